@@ -383,6 +383,28 @@ def side_configs(dev, cpu_seconds: float = 0.0) -> dict:
     return out
 
 
+DUMP_CHAINS = 8192  # the whole sample of one step is 315 MB; 8192 chains' draws are 39 MB, under the dump's 64 MB
+
+
+def dump_chain_ids():
+    """The chains whose draws --dump-outputs writes: a fixed, seeded choice, ascending."""
+    import numpy as np
+
+    return np.sort(np.random.default_rng(SEED).choice(C_PER_GPU, DUMP_CHAINS, replace=False))
+
+
+def dump_outputs(path: str, out, state) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float32 .npy files -- the draws
+    [DUMP_CHAINS, N_COLLECT, DIM] of the chains dump_chain_ids() names and the final positions [C_PER_GPU, DIM]."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    sample = out.index_select(0, torch.from_numpy(dump_chain_ids()).to(out.device)).cpu().numpy()
+    np.save(os.path.join(path, "sample.npy"), sample)
+    np.save(os.path.join(path, "state.npy"), state)
+
+
 EXCHANGE_TEXT = {1: "rccl (ncclAllGather + ncclAllReduce inside libmmcmc.so)", 0: "host (a device is listed twice)",
                  -1: "host FALLBACK: no RCCL library could be loaded", -2: "host FALLBACK: ncclCommInitAll failed"}
 
@@ -526,7 +548,13 @@ def main() -> None:
     ap.add_argument("--pipelined", action="store_true",
                     help="also time sampler and diagnostics as a two-stream pipeline (a measured negative result, DESIGN.md 5.2: "
                          "slower than back to back; off by default so that a profiled run holds only undisturbed launches of the sampling kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's shard) as float32 .npy files: "
+                         f"sample.npy = the draws of {DUMP_CHAINS} chains chosen by a fixed seed [{DUMP_CHAINS}, {N_COLLECT}, {DIM}], "
+                         f"state.npy = every chain's final position [{C_PER_GPU}, {DIM}]")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -535,6 +563,8 @@ def main() -> None:
     # and no launcher environment, runs ONE process over N devices through the library's device group (RCCL inside
     # libmmcmc.so); under torch.distributed.run (WORLD_SIZE set) it is one process per GPU
     if args.group or (args.gpus > 1 and "WORLD_SIZE" not in os.environ):
+        if args.dump_outputs:
+            ap.error("--dump-outputs is written by the one-process-per-GPU path only, not by the device group")
         return main_group(args)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -573,9 +603,14 @@ def main() -> None:
     # every rank owns global chains [rank*C, (rank+1)*C); the init stream is the reference's, sliced per rank
     init_all = init_with_seed(C_PER_GPU * world, DIM, SEED, np.float32)
     init = np.ascontiguousarray(init_all[rank * C_PER_GPU:(rank + 1) * C_PER_GPU])
-    sampler = HMC(RosenbrockND(DIM), init, STEP_SIZE, N_LEAPFROG, device=local_rank).set_seed(SEED)
-    sampler.set_chain_offset(rank * C_PER_GPU)
-    sampler.set_kernel_variant(args.variant)
+
+    def new_sampler():
+        h = HMC(RosenbrockND(DIM), init, STEP_SIZE, N_LEAPFROG, device=local_rank).set_seed(SEED)
+        h.set_chain_offset(rank * C_PER_GPU)
+        h.set_kernel_variant(args.variant)
+        return h
+
+    sampler = new_sampler()
 
     out = torch.empty((C_PER_GPU, N_COLLECT, DIM), dtype=torch.float32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -605,6 +640,12 @@ def main() -> None:
             step()
         torch.cuda.synchronize()
         preroll_steps += 100
+    if preroll_steps:
+        # how many launches the pre-roll made depends on the clocks: the counted steps run on a fresh handle from
+        # init_with_seed, so that the same arguments give the same outputs (--dump-outputs)
+        sampler.close()
+        sampler = new_sampler()
+        sampler.enable_timing(False)
     for _ in range(args.warmup):
         step()
     barrier()
@@ -621,6 +662,8 @@ def main() -> None:
     barrier()
     dt = time.perf_counter() - t0
     kernel_ms_timed_region = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs and rank == 0:  # before the launches below overwrite `out` and advance the chains
+        dump_outputs(args.dump_outputs, out, sampler.state())
     sampler.enable_timing(True)
     # the same kernel one launch at a time (the device idles between launches: slower clocks), reported beside it
     kernel_ms = []

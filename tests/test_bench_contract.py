@@ -37,6 +37,13 @@ def test_bench_decides_group_before_touching_a_gpu():
         assert "torch.distributed.run" not in out.stderr
 
 
+def test_bench_refuses_arguments_it_cannot_honour():
+    for args, why in ((["--steps", "0"], "--steps must be at least 1"),
+                      (["--gpus", "1", "--group", "--dump-outputs", "unused"], "--dump-outputs is written by the one-process-per-GPU path")):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True)
+        assert out.returncode == 2 and why in out.stderr, out.stderr[-500:]
+
+
 def _bench_module():
     import importlib.util
 
@@ -187,6 +194,38 @@ def test_bench_line_contract_and_roofline_is_the_hbm_fraction():
     assert cb["per_thread_over_single_thread"] >= 0.5 or "per_thread_note" in cb
     assert ("ess_per_s" in j) != ("ess_per_s_unconverged" in j)
     assert ("ess_per_s" in j) == (j["split_rhat_max_conventional"] <= 1.05)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_last_timed_step(tmp_path, O):
+    """--dump-outputs writes what the last timed step computed: the same files whatever the pre-roll did (it drives a handle
+    of its own), different ones after one more timed step, and equal to the host build of the engine's arithmetic after
+    warm-up + steps runs from init_with_seed (checked on the first 256 chains)."""
+    import numpy as np
+
+    from mini_mcmc_amd.core import init_with_seed
+
+    def dump(name, steps, preroll):
+        d = tmp_path / name
+        _run(["--steps", str(steps), "--warmup", "1", "--preroll-seconds", str(preroll), "--no-side", "--no-cpu-baseline",
+              "--dump-outputs", str(d)])
+        files = sorted(d.iterdir())
+        assert [f.name for f in files] == ["sample.npy", "state.npy"] and sum(f.stat().st_size for f in files) <= 64 << 20
+        return {f.stem: np.load(f) for f in files}
+
+    a, b, c = dump("a", 2, 0), dump("b", 2, 0.5), dump("c", 3, 0)
+    assert a["sample"].shape == (8192, 400, 3) and a["state"].shape == (65536, 3)
+    assert a["sample"].dtype == a["state"].dtype == np.float32
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+        assert not np.array_equal(a[k], c[k]), k
+    # warm-up 1 + steps 2 = three run(400, 50) from iteration 0: the last one's draws are those of run(400, 950)
+    ref, ref_state, _ = O.engine_host_run("hmc", O.ROSENBROCK_ND, 3, [], init_with_seed(256, 3, 42, np.float32), 0.032, 400,
+                                          950, seed=42, n_leapfrog=10)
+    chains = _bench_module().dump_chain_ids()
+    low = chains[chains < 256]
+    assert low.size > 0 and np.array_equal(a["sample"][:low.size], ref[low])
+    assert np.array_equal(a["state"][:256], ref_state)
 
 
 @pytest.mark.gpu
