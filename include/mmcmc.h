@@ -402,7 +402,10 @@ int mmcmc_nuts_group_destroy(mmcmc_nuts_group *g);
 /* ---- diagnostics: stats.rs ------------------------------------------------------------------------------
  * split_rhat_mean_ess(sample[chains, n, params]) -> (rhat[params], ess[params])   stats.rs:416-423
  * (splitcat :396-402, withinvar :429-477, rhat :425-427 = sqrt(W/var+) as the reference defines it, ess :496-546).
- * sample: [n_chains, n, dim] of dtype, device or host memory; rhat, ess: host [dim] (f32 like the reference). */
+ * sample: [n_chains, n, dim] of dtype, device or host memory; rhat, ess: host [dim] (f32 like the reference).
+ * Shapes: dim < 2^16, n < 2^31, and where the half-chain takes the residue transform (1024 < n/2 <= 131072)
+ * dim x 2048 x max(2, ceil(n/2 / 1024)) < 2^32 -- from dim = 16384 up that cuts the longest half-chains -- whichever kernel
+ * is selected; MMCMC_ERR_SHAPE beyond, decided from the shape before anything is allocated (also for _stats_partials). */
 int mmcmc_split_rhat_mean_ess(const void *sample, int sample_is_device, int dtype, size_t n_chains, size_t n,
                               size_t dim, float *rhat, float *ess, int device, void *stream);
 /* The two halves of the above, for multi-GPU runs (chains sharded over ranks):

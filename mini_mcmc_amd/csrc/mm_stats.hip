@@ -2109,6 +2109,17 @@ static int stats_fft_launch(const StatsFftPlan &p, const void *sample, size_t n_
     return MMCMC_ERR_UNSUPPORTED;
 }
 
+/* The transform paths count bins (dim x N, N = 2048 N1 up to 2^18 beyond 1024 draws per half-chain) in 32 bits: a shape
+ * whose count would wrap is refused from the shape alone, whichever kernel is selected, before anything is allocated */
+static bool stats_bins_fit(size_t n, size_t dim)
+{
+    const size_t m = n / 2;
+    if (m <= 1024 || m > kStatsLongMaxM)
+        return true; /* one wave-level transform (N <= 2048, dim < 2^16) or no transform at all */
+    const uint64_t N = 2048ull * std::max<uint64_t>(2, (m + 1023) / 1024);
+    return (uint64_t)dim * N < (1ull << 32);
+}
+
 /* floats of device workspace stats_partials_impl wants behind `slabs_ws` */
 static size_t stats_ws_floats(size_t n_chains, size_t n, size_t dim, unsigned int n_parts, int device)
 {
@@ -2135,7 +2146,7 @@ static int stats_partials_impl(const void *sample, int dtype, size_t n_chains, s
         (dtype != MMCMC_F32 && dtype != MMCMC_F64))
         return MMCMC_ERR_INVALID_ARG;
     const size_t m = n / 2;
-    if (m < 1 || n >= (1ull << 31) || dim >= (1u << 16))
+    if (m < 1 || n >= (1ull << 31) || dim >= (1u << 16) || !stats_bins_fit(n, dim))
         return MMCMC_ERR_SHAPE;
     int st = check_device(device);
     if (st != MMCMC_OK)
@@ -2540,6 +2551,8 @@ int mmcmc_stats_partials(const void *sample, int dtype, size_t n_chains, size_t 
     static thread_local Ws w;
     if (!sample || n_chains == 0 || dim == 0 || n / 2 < 1)
         return MMCMC_ERR_INVALID_ARG;
+    if (n >= (1ull << 31) || dim >= (1u << 16) || !stats_bins_fit(n, dim))
+        return MMCMC_ERR_SHAPE;
     int st = check_device(device);
     if (st != MMCMC_OK)
         return st;
@@ -2648,7 +2661,7 @@ int mmcmc_split_rhat_mean_ess(const void *sample, int sample_is_device, int dtyp
     if (!sample || !rhat || !ess || n_chains == 0 || dim == 0)
         return MMCMC_ERR_INVALID_ARG;
     const size_t m = n / 2;
-    if (m < 1)
+    if (m < 1 || n >= (1ull << 31) || dim >= (1u << 16) || !stats_bins_fit(n, dim))
         return MMCMC_ERR_SHAPE;
     int st = check_device(device);
     if (st != MMCMC_OK)

@@ -961,7 +961,7 @@ def test_split_rhat_mean_ess_long_chains_vs_oracle(M, O, c, n, p):
 @pytest.mark.gpu
 def test_split_rhat_mean_ess_refuses_shapes_beyond_its_stated_limits(M):
     """The from-global-memory path (half-chains beyond 16 384 draws) states its limits (include/mmcmc.h, advisor r4): 32-bit
-    element and grid counts -> MMCMC_ERR_SHAPE, more than 2^46 lag products (~ten seconds of device time) ->
+    element and grid counts (and the residue transforms' 32-bit bin count, dim x 2048 N1) -> MMCMC_ERR_SHAPE, more than 2^46 lag products (~ten seconds of device time) ->
     MMCMC_ERR_UNSUPPORTED -- decided from the shape alone, before anything reads the sample (a one-element buffer stands in)."""
     import ctypes as C
 
@@ -985,6 +985,13 @@ def test_split_rhat_mean_ess_refuses_shapes_beyond_its_stated_limits(M):
         lib.mmcmc_stats_set_direct_work_limit(1 << 46)
     assert call(64, 33000, 2) == L.OK                       # inside the limits (N1 = 32 residues; values: the parity test above)
     torch.cuda.synchronize()
+    # the residue transforms' bin count dim x 2048 N1 is 32-bit: 16384 x 2^18 = 2^32 and 65535 x 2048 x 33 wrap -> refused from the
+    # shape, before the pinned buffer or the workspace (hundreds of GB here) is asked for; through both entry points
+    f = C.c_void_p(buf.data_ptr())
+    for c, n, d in [(1, 262144, 16384), (1, 65538, 65535), (3, 262145, 16384)]:
+        assert call(c, n, d) == L.ERR_SHAPE, (c, n, d)
+        assert lib.mmcmc_stats_partials(f, L.F32, c, n, d, f, f, f, 0, None) == L.ERR_SHAPE, (c, n, d)
+    assert call(1, 2048, 65536) == L.ERR_SHAPE  # dim < 2^16 on every path
 
 
 @pytest.mark.gpu

@@ -9,7 +9,7 @@
     chain count, run length, iterations per launch, f32 and f64;
   - diagnostics: the power-spectrum kernel against the direct sums (R-hat / ESS to 1e-4 / 2e-3); x: long half-chains
     (N1 residues, any N1) against the direct sums.
-usage: python tools/fuzz_variants.py [seconds per family, default 40] [families: any of d g t n l h s x m, default dgtnlhsm]"""
+usage: python tools/fuzz_variants.py [seconds per family, default 40] [families: any of d g t n l h s x m, default dgtnlhsxm]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -20,7 +20,7 @@ from mini_mcmc_amd.distributions import IsotropicGaussian, RosenbrockND, Standar
 from mini_mcmc_amd.nuts import NUTS
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 40.0
-fam = sys.argv[2] if len(sys.argv) > 2 else "dgtnlhsm"
+fam = sys.argv[2] if len(sys.argv) > 2 else "dgtnlhsxm"
 rng = np.random.default_rng(int(time.time()) & 0xffff)
 print("seed", rng.bit_generator.state["state"]["state"] & 0xffff)
 
