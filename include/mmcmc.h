@@ -34,6 +34,8 @@ extern "C" {
  *   MMCMC_ERR_GROUP_BROKEN; mmcmc_*_group_run blocks again whatever its arguments (100 inferred "asynchronous" from
  *   out_host == NULL && accept_counts == NULL); mmcmc_nuts_set_repacking (100, measured slower, removed) stays removed.
  * 102 (round 6): + mmcmc_rtc_compiler_info; long-chain diagnostics take N1 = ceil(n/2 / 1024) residues (any count).
+ * Later additions that keep 102 (a binding probes them with dlsym): mmcmc_hmc_set_step_size, mmcmc_hmc_set_n_leapfrog,
+ *   mmcmc_hmc_params, mmcmc_hmc_set_state, mmcmc_hmc_run_scheduled.
  * A binding checks mmcmc_version() >= the version it was generated from (rust/mini-mcmc-hip: assert_abi, in every constructor). */
 #define MMCMC_VERSION 102 /* 0.1.2 */
 
@@ -169,6 +171,26 @@ int mmcmc_hmc_sync(mmcmc_hmc *h);
 int mmcmc_hmc_timing(mmcmc_hmc *h, mmcmc_timing *t);
 int mmcmc_hmc_enable_timing(mmcmc_hmc *h, int on);
 int mmcmc_hmc_destroy(mmcmc_hmc *h);
+
+/* The reference's public fields (hmc.rs:41-49: pub step_size, pub n_leapfrog, pub positions) as setters, and scheduled runs.
+ * These entry points are additive: MMCMC_VERSION stays 102, and a binding that must also load an older library probes them
+ * with dlsym.  None of them touches the seed, the chain offset or the iteration counter.
+ *   set_step_size / set_n_leapfrog: mmcmc_hmc_create's checks (step size finite and > 0, n_leapfrog >= 0); they apply from
+ *     the next transition on.  mmcmc_hmc_params reads both back (either pointer may be NULL).
+ *   set_state: [n_chains, dim] of the handle's dtype, host memory (is_device = 0; copied before the call returns) or device
+ *     memory on the handle's device (is_device = 1), ordered on `stream` (NULL: the handle's own) like a run.
+ *   run_scheduled: step_sizes / n_leapfrogs are host arrays of n_discard + n_collect entries.  Defined as, for each k: set
+ *     (step_sizes[k], n_leapfrogs[k]), do one transition, keep the state as sample row k - n_discard when k >= n_discard --
+ *     and equal to that loop bit for bit (samples, final state, accept counts, iteration counter).  Afterwards the handle's
+ *     own step size and leapfrog count are what they were.  Output arguments as mmcmc_hmc_run.  The default kernels of the
+ *     fixed-dimension targets (variants 5 and 2) read the pair per transition in one launch; every other variant runs one
+ *     launch per maximal run of equal pairs (one per transition at worst). */
+int mmcmc_hmc_set_step_size(mmcmc_hmc *h, double step_size);
+int mmcmc_hmc_set_n_leapfrog(mmcmc_hmc *h, int n_leapfrog);
+int mmcmc_hmc_params(mmcmc_hmc *h, double *step_size, int *n_leapfrog);
+int mmcmc_hmc_set_state(mmcmc_hmc *h, const void *positions, int is_device, void *stream);
+int mmcmc_hmc_run_scheduled(mmcmc_hmc *h, size_t n_collect, size_t n_discard, const double *step_sizes,
+                            const int32_t *n_leapfrogs, void *out, int out_is_device, uint64_t *accept_counts, void *stream);
 
 /* ---- NUTS ------------------------------------------------------------------------------------------------
  * NUTS::new(target, initial_positions, target_accept_p)   nuts.rs:123-129 over NUTSChain::new nuts.rs:410-434.

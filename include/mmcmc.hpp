@@ -321,6 +321,49 @@ template <class T> class HMC {
         check(mmcmc_hmc_state(h_, out.data()), "mmcmc_hmc_state");
         return out;
     }
+    /* the reference's public fields (hmc.rs:41-49): from the next transition on */
+    HMC &set_step_size(double step_size)
+    {
+        check(mmcmc_hmc_set_step_size(h_, step_size), "mmcmc_hmc_set_step_size");
+        return *this;
+    }
+    HMC &set_n_leapfrog(int n_leapfrog)
+    {
+        check(mmcmc_hmc_set_n_leapfrog(h_, n_leapfrog), "mmcmc_hmc_set_n_leapfrog");
+        return *this;
+    }
+    double step_size()
+    {
+        double eps = 0;
+        check(mmcmc_hmc_params(h_, &eps, nullptr), "mmcmc_hmc_params");
+        return eps;
+    }
+    int n_leapfrog()
+    {
+        int n = 0;
+        check(mmcmc_hmc_params(h_, nullptr, &n), "mmcmc_hmc_params");
+        return n;
+    }
+    HMC &set_positions(const std::vector<T> &positions)
+    {
+        if (positions.size() != n_chains_ * dim_)
+            throw Error(MMCMC_ERR_SHAPE, "HMC::set_positions");
+        check(mmcmc_hmc_set_state(h_, positions.data(), 0, nullptr), "mmcmc_hmc_set_state");
+        return *this;
+    }
+    /* transition k uses (step_sizes[k], n_leapfrogs[k]), the first size - n_collect are discarded: the loop
+     * set_step_size; set_n_leapfrog; step() bit for bit, in one call */
+    std::vector<T> run_scheduled(const std::vector<double> &step_sizes, const std::vector<int32_t> &n_leapfrogs, size_t n_collect)
+    {
+        if (step_sizes.size() != n_leapfrogs.size() || n_collect > step_sizes.size())
+            throw Error(MMCMC_ERR_INVALID_ARG, "HMC::run_scheduled");
+        std::vector<T> out(n_chains_ * n_collect * dim_);
+        check(mmcmc_hmc_run_scheduled(h_, n_collect, step_sizes.size() - n_collect, step_sizes.data(), n_leapfrogs.data(),
+                                      out.data(), 0, nullptr, nullptr),
+              "mmcmc_hmc_run_scheduled");
+        check(mmcmc_hmc_sync(h_), "mmcmc_hmc_sync");
+        return out;
+    }
 };
 
 /* ---- a target of the user's own: the GPU analogue of `impl GradientTarget for MyDensity` (distributions.rs:65-108).

@@ -88,6 +88,12 @@ SIGNATURES = {
     "mmcmc_hmc_timing": (C.c_int, [_vp, C.POINTER(Timing)]),
     "mmcmc_hmc_destroy": (C.c_int, [_vp]),
     "mmcmc_hmc_set_iters_per_launch": (C.c_int, [_vp, C.c_uint32]),
+    "mmcmc_hmc_set_step_size": (C.c_int, [_vp, C.c_double]),
+    "mmcmc_hmc_set_n_leapfrog": (C.c_int, [_vp, C.c_int]),
+    "mmcmc_hmc_params": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "mmcmc_hmc_set_state": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+    "mmcmc_hmc_run_scheduled": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_int32), _vp, C.c_int,
+                                          C.POINTER(C.c_uint64), _vp]),
     "mmcmc_mh_set_kernel_variant": (C.c_int, [_vp, C.c_int]),
     "mmcmc_hmc_set_kernel_variant": (C.c_int, [_vp, C.c_int]),
     "mmcmc_nuts_create": (C.c_int, [C.POINTER(_vp), _TP, C.POINTER(C.c_double), C.c_size_t, C.c_double, C.c_int, C.c_int]),

@@ -197,6 +197,16 @@ struct Sampler {
     bool want_accept = true; /* this run(): per-chain accept counts requested */
     bool timing_enabled = true;
     mmcmc_timing timing{};
+    /* scheduled runs (mmcmc_hmc_run_scheduled): the device schedule [n + 1] of mm_sched_step<T>, grown on demand, its host
+     * image, and an event after the last run that read them (both are rewritten only once it has passed) */
+    void *d_sched = nullptr;
+    size_t sched_cap = 0;
+    std::vector<unsigned char> h_sched;
+    hipEvent_t ev_sched = nullptr;
+    bool sched_pending = false;
+    /* set for the duration of a scheduled run whose variant has a scheduled kernel: launch_range launches it */
+    const void *sched_run = nullptr;
+    uint32_t sched_iter0 = 0;
 
     size_t esize() const { return dtype == MMCMC_F32 ? 4 : 8; }
 };
@@ -205,7 +215,8 @@ int sampler_create(Sampler **out, int sampler, const mmcmc_target_desc *target, 
                    const void *init, size_t n_chains, int dtype, int device);
 int sampler_destroy(Sampler *s);
 int sampler_run(Sampler *s, size_t n_collect, size_t n_discard, void *out, int out_is_device, uint64_t *accept_counts,
-                void *stream_v, size_t n_total_rows = 0, size_t row0 = 0);
+                void *stream_v, size_t n_total_rows = 0, size_t row0 = 0, const double *sched_eps = nullptr,
+                const int32_t *sched_L = nullptr);
 
 thread_local bool g_in_unit_check = false;
 
@@ -421,6 +432,10 @@ int sampler_destroy(Sampler *s)
         (void)hipFree(s->d_gscratch);
     if (s->d_stage)
         (void)hipFree(s->d_stage);
+    if (s->d_sched)
+        (void)hipFree(s->d_sched);
+    if (s->ev_sched)
+        (void)hipEventDestroy(s->ev_sched);
     (void)hipEventDestroy(s->ev0);
     (void)hipEventDestroy(s->ev1);
     (void)hipStreamDestroy(s->stream);
@@ -462,7 +477,12 @@ int launch_range(Sampler *s, const mm_kernel_entry<T> *k, const mm_tparams<T> &P
     unsigned int grid = (unsigned int)((s->n_chains + s->block - 1) / s->block);
     hipError_t e;
     const bool mh = s->sampler == MM_SAMPLER_MH, l10 = s->n_leapfrog == 10;
-    if (s->variant == 7 && s->user) {
+    if (s->sched_run) {
+        /* a scheduled run on a variant with a scheduled kernel (sched_kernel_ok): (eps, L) per transition from the device */
+        const mm_sched_step<T> *sched = (const mm_sched_step<T> *)s->sched_run;
+        e = s->variant == 5 ? k->run_hmc_split_sched(a, sched, s->sched_iter0, stream)
+                            : k->run_hmc_pp_sched(a, sched, s->sched_iter0, grid, s->block, stream);
+    } else if (s->variant == 7 && s->user) {
         /* the same skeleton (mm_run_kernel_body, PIPE = 2) around the user's functor, from the run-time compiled module */
         /* f32 up to dim 8: the split-role skeleton (four waves per SIMD) where the module has it; else PIPE = 2, one wave per SIMD */
         e = hipErrorNotFound;
@@ -581,10 +601,58 @@ int launch_range(Sampler *s, const mm_kernel_entry<T> *k, const mm_tparams<T> &P
     return MMCMC_OK;
 }
 
+/* does the handle's variant have a kernel that reads (eps, L) per transition?  The split kernel (5, f32 up to dim 8) and
+ * PIPE = 2 (2, and 1 which selects it) of the fixed-dimension targets; every other variant runs a schedule in segments */
+template <class T> bool sched_kernel_ok(const Sampler *s, const mm_kernel_entry<T> *k)
+{
+    if (s->sampler != MM_SAMPLER_HMC || !k || (s->user && s->variant == 7))
+        return false;
+    if (s->variant == 5)
+        return k->run_hmc_split_sched != nullptr;
+    return (s->variant == 1 || s->variant == 2) && k->run_hmc_pp_sched != nullptr;
+}
+
+/* the schedule of a run as mm_sched_step<T> [n + 1] in the handle's device buffer; eps converted as launch_range converts
+ * s->scale.  Entry n ({0, 0}) is read by PIPE = 2's transition past an odd run's end, which changes nothing (ln u = NaN). */
+template <class T> int upload_schedule(Sampler *s, const double *eps, const int32_t *L, size_t n, hipStream_t stream)
+{
+    const size_t bytes = (n + 1) * sizeof(mm_sched_step<T>);
+    if (s->sched_pending) {
+        MM_HIP(hipEventSynchronize(s->ev_sched)); /* the last scheduled run has read both buffers */
+        s->sched_pending = false;
+    }
+    if (bytes > s->sched_cap) {
+        if (s->d_sched)
+            (void)hipFree(s->d_sched);
+        s->d_sched = nullptr;
+        s->sched_cap = 0;
+        MM_HIP(hipMalloc(&s->d_sched, bytes));
+        s->sched_cap = bytes;
+    }
+    if (!s->ev_sched)
+        MM_HIP(hipEventCreateWithFlags(&s->ev_sched, hipEventDisableTiming));
+    s->h_sched.assign(bytes, 0);
+    mm_sched_step<T> *h = reinterpret_cast<mm_sched_step<T> *>(s->h_sched.data());
+    for (size_t i = 0; i < n; ++i) {
+        h[i].eps = (T)eps[i];
+        h[i].n_leapfrog = L[i];
+    }
+    h[n].eps = T(0);
+    h[n].n_leapfrog = 0;
+    MM_HIP(hipMemcpyAsync(s->d_sched, s->h_sched.data(), bytes, hipMemcpyHostToDevice, stream));
+    MM_HIP(hipEventRecord(s->ev_sched, stream)); /* recorded again after the run's launches */
+    s->sched_pending = true;
+    return MMCMC_OK;
+}
+
 /* n_total_rows / row0: the collected rows go to rows [row0, row0 + n_collect) of out [n_chains, n_total_rows, dim] (device
- * memory only when n_total_rows != n_collect): how run_progress fills one sample by several launches (mm_progress.hip) */
+ * memory only when n_total_rows != n_collect): how run_progress fills one sample by several launches (mm_progress.hip).
+ * sched_eps / sched_L (HMC, both or neither, checked by the caller): transition k of the run uses (sched_eps[k], sched_L[k])
+ * -- read per transition by the scheduled kernels, else one launch per maximal run of equal pairs; the handle's own
+ * step size and leapfrog count are what they were afterwards. */
 int sampler_run(Sampler *s, size_t n_collect, size_t n_discard, void *out, int out_is_device,
-                uint64_t *accept_counts, void *stream_v, size_t n_total_rows, size_t row0)
+                uint64_t *accept_counts, void *stream_v, size_t n_total_rows, size_t row0, const double *sched_eps,
+                const int32_t *sched_L)
 {
     if (!s)
         return MMCMC_ERR_INVALID_ARG;
@@ -598,6 +666,27 @@ int sampler_run(Sampler *s, size_t n_collect, size_t n_discard, void *out, int o
         return MMCMC_ERR_SHAPE;
     DeviceGuard g(s->device);
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : s->stream;
+    /* a scheduled run: restores the handle's (eps, L) and leaves launch_range's scheduled mode however it returns */
+    struct SchedScope {
+        Sampler *s;
+        double scale;
+        int n_leapfrog;
+        ~SchedScope()
+        {
+            s->scale = scale;
+            s->n_leapfrog = n_leapfrog;
+            s->sched_run = nullptr;
+        }
+    } sched_scope{s, s->scale, s->n_leapfrog};
+    const bool sched = sched_eps != nullptr;
+    if (sched && (s->dtype == MMCMC_F32 ? sched_kernel_ok<float>(s, s->kf) : sched_kernel_ok<double>(s, s->kd))) {
+        const int st = s->dtype == MMCMC_F32 ? upload_schedule<float>(s, sched_eps, sched_L, n_collect + n_discard, stream)
+                                             : upload_schedule<double>(s, sched_eps, sched_L, n_collect + n_discard, stream);
+        if (st != MMCMC_OK)
+            return st;
+        s->sched_run = s->d_sched;
+        s->sched_iter0 = (uint32_t)s->iter; /* the RUN's first iteration: chunks index the schedule from here */
+    }
     const size_t out_bytes = s->n_chains * n_collect * (size_t)s->dim * s->esize();
     void *d_out = nullptr;
     /* host output: the kernels write a device staging buffer the handle keeps (grown on demand, freed with the handle: a
@@ -630,11 +719,23 @@ int sampler_run(Sampler *s, size_t n_collect, size_t n_discard, void *out, int o
     uint64_t remaining_discard = n_discard, remaining_collect = n_collect, t0 = row0;
     const uint64_t cap = s->iters_per_launch ? s->iters_per_launch : (n_discard + n_collect);
     uint32_t launches = 0;
+    const uint64_t n_run = (uint64_t)n_discard + n_collect;
     if (s->timing_enabled)
         MM_HIP(hipEventRecord(s->ev0, stream));
     while (remaining_discard + remaining_collect > 0) {
-        uint32_t nd = (uint32_t)std::min<uint64_t>(remaining_discard, cap);
-        uint32_t nc = (uint32_t)std::min<uint64_t>(remaining_collect, cap - nd);
+        uint64_t cap_k = cap;
+        if (sched && !s->sched_run) {
+            /* segmented fallback: this launch ends where the pair changes (one launch per transition at worst) */
+            const uint64_t k = n_run - remaining_discard - remaining_collect;
+            uint64_t len = 1;
+            while (len < cap && k + len < n_run && sched_eps[k + len] == sched_eps[k] && sched_L[k + len] == sched_L[k])
+                ++len;
+            cap_k = len;
+            s->scale = sched_eps[k];
+            s->n_leapfrog = sched_L[k];
+        }
+        uint32_t nd = (uint32_t)std::min<uint64_t>(remaining_discard, cap_k);
+        uint32_t nc = (uint32_t)std::min<uint64_t>(remaining_collect, cap_k - nd);
         int st;
         if (s->dtype == MMCMC_F32)
             st = launch_range<float>(s, s->kf, s->Pf, (float *)d_out, n_total_rows, nd, nc, (uint32_t)t0, stream);
@@ -646,6 +747,10 @@ int sampler_run(Sampler *s, size_t n_collect, size_t n_discard, void *out, int o
         remaining_collect -= nc;
         t0 += nc;
         ++launches;
+    }
+    if (s->sched_run) {
+        MM_HIP(hipEventRecord(s->ev_sched, stream));
+        s->sched_pending = true;
     }
     if (s->timing_enabled)
         MM_HIP(hipEventRecord(s->ev1, stream));
@@ -1131,6 +1236,69 @@ int mmcmc_hmc_step(mmcmc_hmc *h, void *stream)
     return h ? sampler_run(h->s, 0, 1, nullptr, 1, nullptr, stream) : MMCMC_ERR_INVALID_ARG;
 }
 int mmcmc_hmc_state(mmcmc_hmc *h, void *out) { return h ? sampler_state(h->s, out) : MMCMC_ERR_INVALID_ARG; }
+/* the reference's public fields (hmc.rs:41-49): step_size, n_leapfrog, positions -- from the next transition on */
+int mmcmc_hmc_set_step_size(mmcmc_hmc *h, double step_size)
+{
+    if (!h || !(step_size > 0.0) || !std::isfinite(step_size)) /* mmcmc_hmc_create's check */
+        return MMCMC_ERR_INVALID_ARG;
+    h->s->scale = step_size;
+    return MMCMC_OK;
+}
+int mmcmc_hmc_set_n_leapfrog(mmcmc_hmc *h, int n_leapfrog)
+{
+    if (!h || n_leapfrog < 0)
+        return MMCMC_ERR_INVALID_ARG;
+    h->s->n_leapfrog = n_leapfrog;
+    return MMCMC_OK;
+}
+int mmcmc_hmc_params(mmcmc_hmc *h, double *step_size, int *n_leapfrog)
+{
+    if (!h)
+        return MMCMC_ERR_INVALID_ARG;
+    if (step_size)
+        *step_size = h->s->scale;
+    if (n_leapfrog)
+        *n_leapfrog = h->s->n_leapfrog;
+    return MMCMC_OK;
+}
+int mmcmc_hmc_set_state(mmcmc_hmc *h, const void *positions, int is_device, void *stream)
+{
+    if (!h || !positions)
+        return MMCMC_ERR_INVALID_ARG;
+    Sampler *s = h->s;
+    DeviceGuard g(s->device);
+    if (is_device) {
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, positions) != hipSuccess) {
+            (void)hipGetLastError();
+            return MMCMC_ERR_INVALID_ARG;
+        }
+        if ((attr.type != hipMemoryTypeDevice && !attr.isManaged) || attr.device != s->device)
+            return MMCMC_ERR_INVALID_ARG;
+    }
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    /* every kernel variant derives log-density and gradient from the state at launch: nothing else to invalidate */
+    MM_HIP(hipMemcpyAsync(s->d_state, positions, s->n_chains * (size_t)s->dim * s->esize(),
+                          is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if (!is_device)
+        MM_HIP(hipStreamSynchronize(st)); /* the caller's host buffer is free again on return */
+    return MMCMC_OK;
+}
+int mmcmc_hmc_run_scheduled(mmcmc_hmc *h, size_t n_collect, size_t n_discard, const double *step_sizes,
+                            const int32_t *n_leapfrogs, void *out, int out_is_device, uint64_t *accept_counts, void *stream)
+{
+    if (!h)
+        return MMCMC_ERR_INVALID_ARG;
+    const size_t n = n_collect + n_discard;
+    if (n == 0)
+        return MMCMC_OK;
+    if (!step_sizes || !n_leapfrogs)
+        return MMCMC_ERR_INVALID_ARG;
+    for (size_t k = 0; k < n; ++k)
+        if (!(step_sizes[k] > 0.0) || !std::isfinite(step_sizes[k]) || n_leapfrogs[k] < 0)
+            return MMCMC_ERR_INVALID_ARG;
+    return sampler_run(h->s, n_collect, n_discard, out, out_is_device, accept_counts, stream, 0, 0, step_sizes, n_leapfrogs);
+}
 int mmcmc_hmc_sync(mmcmc_hmc *h) { return h ? sampler_sync(h->s) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_hmc_timing(mmcmc_hmc *h, mmcmc_timing *t) { return h ? sampler_timing(h->s, t) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_hmc_destroy(mmcmc_hmc *h)

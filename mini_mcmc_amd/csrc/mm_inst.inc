@@ -6,9 +6,30 @@
 #include "mm_kernels.h"
 #include "mm_split_kernels.h"
 
+/* the scheduled split kernel's launcher where it is instantiated, else null */
+template <class T, class Tgt, int QP, int NN, int RBF, int NT, bool ON> struct mm_split_sched_fn {
+    static constexpr hipError_t (*ptr)(const mm_run_args<T> &, const mm_sched_step<T> *, unsigned int, hipStream_t) = nullptr;
+};
+template <class T, class Tgt, int QP, int NN, int RBF, int NT> struct mm_split_sched_fn<T, Tgt, QP, NN, RBF, NT, true> {
+    static constexpr hipError_t (*ptr)(const mm_run_args<T> &, const mm_sched_step<T> *, unsigned int, hipStream_t) =
+        &mm_launch_run_split_sched<T, Tgt, QP, NN, RBF, NT>;
+};
+
+/* the scheduled PIPE = 2 launcher where variant 2 can be a handle's default: not above dim 16 (the plain kernel is the default
+ * there) and not for the dense Gaussian at 16 / 32 (the lane-group kernel is; its f32 PIPE = 2 form spills with a schedule) */
+template <class T, class Tgt, bool ON> struct mm_pp_sched_fn {
+    static constexpr hipError_t (*ptr)(const mm_run_args<T> &, const mm_sched_step<T> *, unsigned int, unsigned int, unsigned int,
+                                       hipStream_t) = nullptr;
+};
+template <class T, class Tgt> struct mm_pp_sched_fn<T, Tgt, true> {
+    static constexpr hipError_t (*ptr)(const mm_run_args<T> &, const mm_sched_step<T> *, unsigned int, unsigned int, unsigned int,
+                                       hipStream_t) = &mm_launch_run_sched<T, Tgt>;
+};
+
 /* the split kernel's launcher where it is instantiated (dim <= 8: the noise ring of larger dims does not fit), else null */
 template <class T, class Tgt, int SAMPLER, int LCT, bool ON> struct mm_split_fn {
     static constexpr hipError_t (*ptr)(const mm_run_args<T> &, hipStream_t) = nullptr;
+    static constexpr hipError_t (*sched)(const mm_run_args<T> &, const mm_sched_step<T> *, unsigned int, hipStream_t) = nullptr;
 };
 template <class T, class Tgt, int SAMPLER, int LCT> struct mm_split_fn<T, Tgt, SAMPLER, LCT, true> {
     /* f32: three noise waves per pair (1024-thread workgroups, four waves per SIMD; mm_split_kernels.h); f64 keeps one
@@ -20,6 +41,10 @@ template <class T, class Tgt, int SAMPLER, int LCT> struct mm_split_fn<T, Tgt, S
     static constexpr bool pf = SAMPLER == MM_SAMPLER_HMC && nn == 3 && mm_split_hmc_pf<T, Tgt::dim>::ok;
     static constexpr hipError_t (*ptr)(const mm_run_args<T> &, hipStream_t) =
         &mm_launch_run_split<T, Tgt, SAMPLER, LCT, qp, nn, (pf ? 8 : 0), (pf ? 2 : MM_SPLIT_NTILE(SAMPLER == MM_SAMPLER_MH))>;
+    /* the scheduled form of the run-time L HMC instance above (f32 only: the split kernel is the f32 default) */
+    static constexpr hipError_t (*sched)(const mm_run_args<T> &, const mm_sched_step<T> *, unsigned int, hipStream_t) =
+        mm_split_sched_fn<T, Tgt, qp, nn, (pf ? 8 : 0), (pf ? 2 : MM_SPLIT_NTILE(false)),
+                          SAMPLER == MM_SAMPLER_HMC && LCT == 0 && sizeof(T) == 4>::ptr;
 };
 
 #define MM_ENTRY(KIND, DIM)                                                                                       \
@@ -35,7 +60,10 @@ template <class T, class Tgt, int SAMPLER, int LCT> struct mm_split_fn<T, Tgt, S
             mm_split_fn<MM_INST_T, mm_target<MM_INST_T, KIND, (DIM <= 8 ? DIM : 1)>, MM_SAMPLER_MH, 0, (DIM <= 8)>::ptr,  \
             mm_split_fn<MM_INST_T, mm_target<MM_INST_T, KIND, (DIM <= 8 ? DIM : 1)>, MM_SAMPLER_HMC, 0, (DIM <= 8)>::ptr, \
             mm_split_fn<MM_INST_T, mm_target<MM_INST_T, KIND, (DIM <= 8 ? DIM : 1)>, MM_SAMPLER_HMC,                      \
-                        ((DIM <= 8 && KIND != MM_GAUSSIAN_ND) ? 10 : 0), (DIM <= 8)>::ptr                                 \
+                        ((DIM <= 8 && KIND != MM_GAUSSIAN_ND) ? 10 : 0), (DIM <= 8)>::ptr,                                \
+            /* scheduled runs (mmcmc_hmc_run_scheduled): the run-time L instances read (eps, L) per transition */          \
+            mm_pp_sched_fn<MM_INST_T, mm_target<MM_INST_T, KIND, DIM>, (DIM <= 16 && !(KIND == MM_GAUSSIAN_ND && DIM >= 16))>::ptr, \
+            mm_split_fn<MM_INST_T, mm_target<MM_INST_T, KIND, (DIM <= 8 ? DIM : 1)>, MM_SAMPLER_HMC, 0, (DIM <= 8)>::sched \
     }
 
 #define MM_ENTRY_ND(KIND)                                                                                         \

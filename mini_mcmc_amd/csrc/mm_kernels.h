@@ -47,6 +47,30 @@ template <class T> struct mm_run_args {
     unsigned long long n_total; /* row count of `out` per chain (n_collect of the whole run) */
 };
 
+/* one entry of a scheduled run's (eps, L) schedule (mm_api.hip: mmcmc_hmc_run_scheduled): transition k of the run uses
+ * sched[k]; eps already in the element type, converted as the launcher converts the handle's step size */
+template <class T> struct mm_sched_step {
+    T eps;
+    int n_leapfrog;
+};
+
+/* (eps, L) of transition iter_t: the run's schedule (SCHED) or the launch's fixed pair.  iter_t is wave-uniform; the index
+ * goes through readfirstlane so that the read is a scalar load and the leapfrog loop's exit test a scalar branch.  The
+ * host pads the schedule by one entry: PIPE = 2 hands the transition past an odd run's end ln u = NaN, and reads its pair. */
+template <class T, bool SCHED>
+__device__ __forceinline__ void mm_sched_at(const mm_run_args<T> &a, const mm_sched_step<T> *sched, unsigned int sched_iter0,
+                                            unsigned int iter_t, T *eps, int *n_leapfrog)
+{
+    if constexpr (SCHED) {
+        const unsigned int k = __builtin_amdgcn_readfirstlane(iter_t - sched_iter0);
+        *eps = sched[k].eps;
+        *n_leapfrog = sched[k].n_leapfrog;
+    } else {
+        *eps = a.scale;
+        *n_leapfrog = a.n_leapfrog;
+    }
+}
+
 constexpr int mm_gcd_c(int a, int b) { return b == 0 ? a : mm_gcd_c(b, a % b); }
 
 /* TILE_T iterations of 64 chains staged per flush */
@@ -224,9 +248,12 @@ __device__ __forceinline__ void mm_flush_tile_raw(T *out, unsigned long long n_t
  *             Box-Muller / log arithmetic packed across the two iterations (v_pk_*_f32) -- next to transitions t, t+1.
  * LCT > 0: compile-time leapfrog count (the loop is unrolled into that block).  Results are bit-identical for
  * every (PIPE, LCT): all variants evaluate the same functions (mm_rng.h, mm_samplers.h). */
-template <class T, class Tgt, int SAMPLER, int PIPE = 0, int LCT = 0>
-__device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a)
+/* SCHED: HMC with PIPE = 2 only -- transition t takes (eps, L) from sched[t - sched_iter0] (mm_sched_at), run-time L */
+template <class T, class Tgt, int SAMPLER, int PIPE = 0, int LCT = 0, bool SCHED = false>
+__device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a, const mm_sched_step<T> *sched = nullptr,
+                                                   unsigned int sched_iter0 = 0)
 {
+    static_assert(!SCHED || (PIPE == 2 && LCT == 0 && SAMPLER == MM_SAMPLER_HMC), "scheduled runs: HMC, PIPE = 2, run-time L");
     constexpr int D = Tgt::dim;
     using Tile = mm_tile<T, D>;
     constexpr int TILE_T = Tile::tile_t, STRIDE = Tile::stride;
@@ -303,10 +330,15 @@ __device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a)
         unsigned int n_acc32 = 0;
         /* every lambda here MUST be inlined: an out-of-line call that captures x / g / lp by reference pins them (and the
          * kernel arguments) in scratch memory for the whole kernel -- what the compiler did for the larger targets */
-        auto transition = [&](T *z, T ln_u) __attribute__((always_inline)) {
+        auto transition = [&](T *z, T ln_u, unsigned int iter_t) __attribute__((always_inline)) {
             /* accepts are counted inside the step (one add under the accept mask) and the wave's total is summed once at
              * the end: a select, a ballot + s_bcnt1 and a 64-bit scalar add per transition were six issue slots */
-            if (SAMPLER == MM_SAMPLER_HMC)
+            if constexpr (SCHED) {
+                T eps;
+                int n_leapfrog;
+                mm_sched_at<T, SCHED>(a, sched, sched_iter0, iter_t, &eps, &n_leapfrog);
+                (void)mm_hmc_step_noise<T, Tgt, 0>(a.P, eps, n_leapfrog, x, &lp, g, z, ln_u, mm_no_hook(), &n_acc32);
+            } else if (SAMPLER == MM_SAMPLER_HMC)
                 (void)mm_hmc_step_noise<T, Tgt, LCT>(a.P, a.scale, a.n_leapfrog, x, &lp, g, z, ln_u, mm_no_hook(), &n_acc32);
             else
                 (void)mm_mh_step_noise<T, Tgt>(a.P, a.scale, x, &lp, z, ln_u, &n_acc32);
@@ -320,8 +352,8 @@ __device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a)
             for (unsigned int i = 0; i < n; i += 2) {
                 T zna[D], znb[D], lnna, lnnb;
                 mm_draw_noise_pair<D, Tab, true, MHP>(a.seed, chain, it + 2u, zna, &lnna, znb, &lnnb, tab);
-                transition(za, lna);
-                transition(zb, (i + 1 < n) ? lnb : never);
+                transition(za, lna, it);
+                transition(zb, (i + 1 < n) ? lnb : never, it + 1u);
                 MM_UNROLL
                 for (int k = 0; k < D; ++k) {
                     za[k] = zna[k];
@@ -345,11 +377,11 @@ __device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a)
                 for (unsigned int i = 0; i < nt; i += 2) {
                     T zna[D], znb[D], lnna, lnnb;
                     mm_draw_noise_pair<D, Tab, true, MHP>(a.seed, chain, it + 2u, zna, &lnna, znb, &lnnb, tab);
-                    transition(za, lna);
+                    transition(za, lna, it);
                     MM_UNROLL
                     for (int k = 0; k < D; ++k)
                         dst[k] = x[k];
-                    transition(zb, (i + 1 < nt) ? lnb : never);
+                    transition(zb, (i + 1 < nt) ? lnb : never, it + 1u);
                     if (TILE_T % 2 == 0 || i + 1 < nt) { /* row nt of an odd tile: inside an even TILE_T, never flushed */
                         MM_UNROLL
                         for (int k = 0; k < D; ++k)
@@ -421,6 +453,14 @@ __global__ __launch_bounds__(256) void mm_run_kernel(const mm_run_args<T> a)
     mm_run_kernel_body<T, Tgt, SAMPLER, PIPE, LCT>(a);
 }
 
+/* a scheduled run's kernel: the runtime-L PIPE = 2 instance reading (eps, L) per transition; sched is only read */
+template <class T, class Tgt>
+__global__ __launch_bounds__(256) void mm_run_kernel_sched(const mm_run_args<T> a, const mm_sched_step<T> *__restrict__ sched,
+                                                           const unsigned int sched_iter0)
+{
+    mm_run_kernel_body<T, Tgt, MM_SAMPLER_HMC, 2, 0, true>(a, sched, sched_iter0);
+}
+
 /* BatchedGradientTarget::unnorm_logp_batch / unnorm_logp_and_grad for n rows (parity tests) */
 template <class T, class Tgt>
 __global__ void mm_logp_grad_kernel(const mm_tparams<T> P, const T *x, T *logp, T *grad, unsigned long long n)
@@ -470,6 +510,15 @@ hipError_t mm_launch_run(const mm_run_args<T> &a, unsigned int grid, unsigned in
 }
 
 template <class T, class Tgt>
+hipError_t mm_launch_run_sched(const mm_run_args<T> &a, const mm_sched_step<T> *sched, unsigned int sched_iter0, unsigned int grid,
+                               unsigned int block, hipStream_t stream)
+{
+    const size_t lds = mm_tile<T, Tgt::dim>::lds_bytes_table + (size_t)(block / 64) * mm_tile<T, Tgt::dim>::lds_bytes_per_wave;
+    hipLaunchKernelGGL((mm_run_kernel_sched<T, Tgt>), dim3(grid), dim3(block), lds, stream, a, sched, sched_iter0);
+    return hipGetLastError();
+}
+
+template <class T, class Tgt>
 hipError_t mm_launch_logp_grad(const mm_tparams<T> &P, const T *x, T *logp, T *grad, unsigned long long n,
                                hipStream_t stream)
 {
@@ -503,6 +552,9 @@ template <class T> struct mm_kernel_entry {
     hipError_t (*run_mh_split)(const mm_run_args<T> &, hipStream_t);
     hipError_t (*run_hmc_split)(const mm_run_args<T> &, hipStream_t);
     hipError_t (*run_hmc_split10)(const mm_run_args<T> &, hipStream_t); /* L = 10 unrolled */
+    /* scheduled runs (mm_sched_step): PIPE = 2 with run-time L; the split kernel (f32, dim <= 8, else null) */
+    hipError_t (*run_hmc_pp_sched)(const mm_run_args<T> &, const mm_sched_step<T> *, unsigned int, unsigned int, unsigned int, hipStream_t);
+    hipError_t (*run_hmc_split_sched)(const mm_run_args<T> &, const mm_sched_step<T> *, unsigned int, hipStream_t);
 };
 
 template <class T> struct mm_noise_entry {

@@ -165,9 +165,14 @@ __device__ unsigned long long mm_split_prof[2][3]; /* [role][barrier wait / tota
  * other's LDS and issue latencies where the step is short (MH).  RBF: ring half (0 = the plan's choice). */
 /* the kernel proper is a device function so that a run-time compiled translation unit (user targets, csrc/mm_rtc.hip) can
  * wrap it in an extern "C" kernel of its own, like mm_run_kernel_body */
-template <class T, class Tgt, int SAMPLER, int LCT = 0, int QP = 0, int NN = 1, int RBF = 0, int NT = MM_SPLIT_NTILE(SAMPLER == MM_SAMPLER_MH), int PW = 4>
-__device__ __forceinline__ void mm_run_split_body(const mm_run_args<T> &a)
+/* SCHED (HMC, run-time L): the transition wave takes transition t's (eps, L) from sched[t - sched_iter0] (mm_sched_at); the
+ * noise waves do not depend on them */
+template <class T, class Tgt, int SAMPLER, int LCT = 0, int QP = 0, int NN = 1, int RBF = 0, int NT = MM_SPLIT_NTILE(SAMPLER == MM_SAMPLER_MH), int PW = 4,
+          bool SCHED = false>
+__device__ __forceinline__ void mm_run_split_body(const mm_run_args<T> &a, const mm_sched_step<T> *sched = nullptr,
+                                                  unsigned int sched_iter0 = 0)
 {
+    static_assert(!SCHED || (LCT == 0 && SAMPLER == MM_SAMPLER_HMC), "scheduled runs: HMC, run-time L");
     constexpr int D = Tgt::dim;
     static_assert(PW == 4 || PW == 2 || PW == 1, "wave pairs per workgroup");
     using Plan = mm_split_plan<T, D, SAMPLER == MM_SAMPLER_MH, RBF, NT, PW>;
@@ -343,7 +348,12 @@ __device__ __forceinline__ void mm_run_split_body(const mm_run_args<T> &a)
         *ln_u = row[D];
     };
     auto transition = [&](T *z, T ln_u, unsigned int iter_t) __attribute__((always_inline)) {
-        if (SAMPLER == MM_SAMPLER_HMC)
+        if constexpr (SCHED) {
+            T eps;
+            int n_leapfrog;
+            mm_sched_at<T, SCHED>(a, sched, sched_iter0, iter_t, &eps, &n_leapfrog);
+            (void)mm_hmc_step_noise<T, Tgt, 0>(a.P, eps, n_leapfrog, x, &lp, g, z, ln_u, mm_no_hook(), &n_acc32);
+        } else if (SAMPLER == MM_SAMPLER_HMC)
             (void)mm_hmc_step_noise<T, Tgt, LCT>(a.P, a.scale, a.n_leapfrog, x, &lp, g, z, ln_u, mm_no_hook(), &n_acc32);
         else if constexpr (UFILT && MHP)
             (void)mm_mh_step_accept<T, Tgt>(a.P, a.scale, x, &lp, z, mm_accept_mhp_f32<Tab>{ln_u, a.seed, chain, iter_t, tab}, &n_acc32); /* `ln_u` holds u_hi */
@@ -520,6 +530,13 @@ __global__ __launch_bounds__(256 * (1 + NN)) void mm_run_split_kernel(const mm_r
 {
     mm_run_split_body<T, Tgt, SAMPLER, LCT, QP, NN, RBF, NT>(a);
 }
+/* a scheduled run's split kernel: the run-time L HMC instance reading (eps, L) per transition; sched is only read */
+template <class T, class Tgt, int QP = 0, int NN = 1, int RBF = 0, int NT = MM_SPLIT_NTILE(false)>
+__global__ __launch_bounds__(256 * (1 + NN)) void mm_run_split_sched_kernel(const mm_run_args<T> a, const mm_sched_step<T> *__restrict__ sched,
+                                                                           const unsigned int sched_iter0)
+{
+    mm_run_split_body<T, Tgt, MM_SAMPLER_HMC, 0, QP, NN, RBF, NT, 4, true>(a, sched, sched_iter0);
+}
 /* workgroup = PW pairs (PW = 1, 2): 64 PW (1 + NN) threads, 1 + NN waves per SIMD as before (4 / PW workgroups per CU) */
 template <class T, class Tgt, int SAMPLER, int PW, int LCT = 0, int QP = 0, int NN = 3, int RBF = 0, int NT = MM_SPLIT_NTILE(SAMPLER == MM_SAMPLER_MH)>
 __global__ __launch_bounds__(64 * PW * (1 + NN)) __attribute__((amdgpu_waves_per_eu(1 + NN, 1 + NN))) void mm_run_splitw_kernel(const mm_run_args<T> a)
@@ -547,6 +564,26 @@ hipError_t mm_launch_run_split(const mm_run_args<T> &a, hipStream_t stream)
     }
     const unsigned int grid = (unsigned int)((a.n_chains + 255ull) / 256ull);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * (1 + NN)), Plan::lds_bytes, stream, a);
+    return hipGetLastError();
+}
+template <class T, class Tgt, int QP = 0, int NN = 1, int RBF = 0, int NT = MM_SPLIT_NTILE(false)>
+hipError_t mm_launch_run_split_sched(const mm_run_args<T> &a, const mm_sched_step<T> *sched, unsigned int sched_iter0, hipStream_t stream)
+{
+    using Plan = mm_split_plan<T, Tgt::dim, false, RBF, NT>;
+    static std::atomic<unsigned long long> attr_set{0}; /* as mm_launch_run_split */
+    auto kern = mm_run_split_sched_kernel<T, Tgt, QP, NN, RBF, NT>;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev >= 64 || !((attr_set >> dev) & 1ull)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)Plan::lds_bytes);
+        if (e != hipSuccess)
+            return e;
+        if (dev < 64)
+            attr_set |= 1ull << dev;
+    }
+    const unsigned int grid = (unsigned int)((a.n_chains + 255ull) / 256ull);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * (1 + NN)), Plan::lds_bytes, stream, a, sched, sched_iter0);
     return hipGetLastError();
 }
 template <class T, class Tgt, int SAMPLER, int PW, int LCT = 0, int QP = 0, int NN = 3, int RBF = 0, int NT = MM_SPLIT_NTILE(SAMPLER == MM_SAMPLER_MH)>

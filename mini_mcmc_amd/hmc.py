@@ -25,7 +25,6 @@ class HMC(_Sampler):
         self.n_chains, self.dim = init.shape
         self.dtype = init.dtype.type
         self.device = device
-        self.step_size, self.n_leapfrog = float(step_size), int(n_leapfrog)
         if target.dim != self.dim:
             if type(target).__name__ in ("RosenbrockND", "StandardNormal"):
                 target = type(target)(self.dim)
@@ -36,7 +35,7 @@ class HMC(_Sampler):
         self.target = target
         d = target.desc()
         st = L.lib().mmcmc_hmc_create(C.byref(self._h), C.byref(d), init.ctypes.data, self.n_chains,
-                                      self.step_size, self.n_leapfrog,
+                                      float(step_size), int(n_leapfrog),
                                       L.F32 if self.dtype == np.float32 else L.F64, device)
         L.check(st, "mmcmc_hmc_create")
 
@@ -55,10 +54,130 @@ class HMC(_Sampler):
         L.check(L.lib().mmcmc_hmc_step(self._h, None), "mmcmc_hmc_step")
         L.check(L.lib().mmcmc_hmc_sync(self._h), "mmcmc_hmc_sync")
 
+    # The reference's public fields (hmc.rs:41-49): setting one applies from the next transition on; seed, chain offset and
+    # iteration counter are untouched.
+    def _params(self):
+        eps, n = C.c_double(), C.c_int()
+        L.check(L.lib().mmcmc_hmc_params(self._h, C.byref(eps), C.byref(n)), "mmcmc_hmc_params")
+        return eps.value, n.value
+
+    @property
+    def step_size(self) -> float:
+        """hmc.rs:43 `step_size`."""
+        return self._params()[0]
+
+    @step_size.setter
+    def step_size(self, eps: float) -> None:
+        L.check(L.lib().mmcmc_hmc_set_step_size(self._h, float(eps)), "mmcmc_hmc_set_step_size")
+
+    @property
+    def n_leapfrog(self) -> int:
+        """hmc.rs:46 `n_leapfrog`."""
+        return self._params()[1]
+
+    @n_leapfrog.setter
+    def n_leapfrog(self, n: int) -> None:
+        L.check(L.lib().mmcmc_hmc_set_n_leapfrog(self._h, int(n)), "mmcmc_hmc_set_n_leapfrog")
+
     @property
     def positions(self) -> np.ndarray:
         """hmc.rs:49 `positions` [n_chains, D]."""
         return self.state()
+
+    @positions.setter
+    def positions(self, x) -> None:
+        """[n_chains, D] of the handle's dtype: a numpy array, or a contiguous torch tensor on the handle's device (copied on
+        torch's current stream, like run(to="torch"))."""
+        if type(x).__module__.startswith("torch"):
+            import torch
+
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            if (x.dtype != tdt or tuple(x.shape) != (self.n_chains, self.dim) or not x.is_contiguous() or x.device.type != "cuda"
+                    or x.device.index != self.device):
+                raise ValueError(f"positions: a contiguous {tdt} tensor [{self.n_chains}, {self.dim}] on cuda:{self.device}")
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            L.check(L.lib().mmcmc_hmc_set_state(self._h, C.c_void_p(x.data_ptr()), 1, C.c_void_p(stream)), "mmcmc_hmc_set_state")
+            return
+        a = np.asarray(x)
+        if a.shape != (self.n_chains, self.dim):
+            raise ValueError(f"positions: shape {a.shape} != ({self.n_chains}, {self.dim})")
+        a = np.ascontiguousarray(a, dtype=self.dtype)
+        L.check(L.lib().mmcmc_hmc_set_state(self._h, a.ctypes.data, 0, None), "mmcmc_hmc_set_state")
+
+    def run_scheduled(self, step_sizes, n_leapfrogs, n_collect: int, to: str = "numpy", accept_counts: bool = True):
+        """Transition k of the run uses (step_sizes[k], n_leapfrogs[k]); the first len - n_collect transitions are discarded.
+        Bit for bit the loop `step_size = eps_k; n_leapfrog = L_k; step()`, keeping the last n_collect states, in one call (one
+        launch on the default kernels of the fixed-dimension targets).  step_size / n_leapfrog are unchanged afterwards.
+        Returns the sample [n_chains, n_collect, dim] like run()."""
+        eps = np.ascontiguousarray(step_sizes, dtype=np.float64).reshape(-1)
+        nl = np.ascontiguousarray(n_leapfrogs, dtype=np.int32).reshape(-1)
+        if eps.shape != nl.shape:
+            raise ValueError("step_sizes and n_leapfrogs differ in length")
+        n_collect = int(n_collect)
+        if not 0 <= n_collect <= eps.size:
+            raise ValueError(f"n_collect {n_collect} outside [0, {eps.size}]")
+        n_discard = eps.size - n_collect
+        epsp = eps.ctypes.data_as(C.POINTER(C.c_double))
+        nlp = nl.ctypes.data_as(C.POINTER(C.c_int32))
+        acc = np.zeros(self.n_chains, dtype=np.uint64) if accept_counts else None
+        accp = acc.ctypes.data_as(C.POINTER(C.c_uint64)) if accept_counts else None
+        fn = L.lib().mmcmc_hmc_run_scheduled
+        if to == "torch":
+            import torch
+
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            out = torch.empty((self.n_chains, n_collect, self.dim), dtype=tdt, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            L.check(fn(self._h, n_collect, n_discard, epsp, nlp, C.c_void_p(out.data_ptr()), 1, accp, C.c_void_p(stream)),
+                    "mmcmc_hmc_run_scheduled")
+        else:
+            out = np.empty((self.n_chains, n_collect, self.dim), dtype=self.dtype)
+            L.check(fn(self._h, n_collect, n_discard, epsp, nlp, out.ctypes.data, 0, accp, None), "mmcmc_hmc_run_scheduled")
+            L.check(L.lib().mmcmc_hmc_sync(self._h), "mmcmc_hmc_sync")
+        self.accept_counts = acc
+        return out
+
+
+def jitter_schedule(n_blocks: int, block: int, eps_range, leapfrog_range, schedule_seed: int = 7):
+    """Per-transition (step_sizes [n_blocks * block] float64, n_leapfrogs int32) holding one (eps_k, L_k) per block of `block`
+    transitions, eps_k ~ U(eps_range), L_k ~ U{leapfrog_range}, drawn from numpy's PCG64(schedule_seed) in run_chain_of_handles'
+    order (eps, then L, per block): block = its n_per_launch gives its sequence of (eps, L)."""
+    rng = np.random.default_rng(schedule_seed)
+    eps = np.empty(n_blocks, dtype=np.float64)
+    nl = np.empty(n_blocks, dtype=np.int32)
+    for k in range(n_blocks):
+        eps[k] = float(rng.uniform(eps_range[0], eps_range[1]))
+        nl[k] = int(rng.integers(leapfrog_range[0], leapfrog_range[1] + 1))
+    return np.repeat(eps, block), np.repeat(nl, block)
+
+
+def run_jittered(target: Target, initial_positions, eps_range, leapfrog_range, block: int, burn_blocks: int, keep_blocks: int,
+                 seed: int = 42, schedule_seed: int = 7, device: int = 0):
+    """run_chain_of_handles' workload on ONE handle: the same (eps_k, L_k) per block of `block` transitions (jitter_schedule),
+    one run_scheduled call -- no host round trip of the state between blocks.  Each transition leaves the target invariant, so
+    does the sequence; the noise stream is the handle's (seed), not run_chain_of_handles' seed + k per launch.  Returns
+    (sample [n_chains, keep_blocks * block, dim] as a torch tensor on the device, info) with run_chain_of_handles' info keys and
+    wall_ms (the call, synchronised, host clock).  accept_rate is over all transitions, the burned blocks included."""
+    import time
+
+    import torch
+
+    eps, nl = jitter_schedule(burn_blocks + keep_blocks, block, eps_range, leapfrog_range, schedule_seed)
+    h = HMC(target, initial_positions, float(eps[0]), int(nl[0]), device=device).set_seed(seed)
+    n_chains = h.n_chains
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    t = h.run_scheduled(eps, nl, keep_blocks * block, to="torch")
+    torch.cuda.synchronize(device)
+    wall_ms = (time.perf_counter() - t0) * 1e3
+    kernel_ms = float(h.timing()["kernel_ms"])
+    info = {"kernel_ms": kernel_ms, "launches": int(h.timing()["n_launches"]), "leapfrogs": float(n_chains) * float(nl.astype(np.float64).sum()),
+            "accept_rate": float(h.accept_counts.mean()) / len(eps) if len(eps) else 0.0,
+            "schedule_head": [(float(eps[k * block]), int(nl[k * block])) for k in range(min(4, burn_blocks + keep_blocks))],
+            "wall_ms": wall_ms}
+    h.close()
+    return t, info
 
 
 def run_chain_of_handles(target: Target, initial_positions, eps_range, leapfrog_range, n_per_launch: int, burn_launches: int,

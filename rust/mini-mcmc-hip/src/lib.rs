@@ -226,6 +226,37 @@ impl<T: GpuFloat> GpuHmc<T> {
         check(unsafe { sys::mmcmc_hmc_state(self.h, out.as_mut_ptr() as *mut c_void) })?;
         Ok(out)
     }
+    /// `hmc.step_size = eps` (hmc.rs:43, a public field): from the next transition on
+    pub fn set_step_size(&mut self, step_size: f64) -> Result<(), MmcmcError> {
+        check(unsafe { sys::mmcmc_hmc_set_step_size(self.h, step_size) })
+    }
+    /// `hmc.n_leapfrog = n` (hmc.rs:46, a public field): from the next transition on
+    pub fn set_n_leapfrog(&mut self, n_leapfrog: usize) -> Result<(), MmcmcError> {
+        check(unsafe { sys::mmcmc_hmc_set_n_leapfrog(self.h, n_leapfrog as c_int) })
+    }
+    /// `hmc.positions = x` (hmc.rs:49, a public field): `[n_chains, dim]`
+    pub fn set_positions(&mut self, positions: &Array2<T>) -> Result<(), MmcmcError> {
+        if positions.dim() != (self.n_chains, self.dim) {
+            return check(sys::MMCMC_ERR_SHAPE);
+        }
+        let owned = positions.as_standard_layout();
+        check(unsafe { sys::mmcmc_hmc_set_state(self.h, owned.as_ptr() as *const c_void, 0, null_mut()) })
+    }
+    /// Transition k uses `(step_sizes[k], n_leapfrogs[k])`; the first `len - n_collect` are discarded: bit for bit the loop
+    /// `set_step_size; set_n_leapfrog; step()` in one call (`mmcmc_hmc_run_scheduled`), `[n_chains, n_collect, dim]`
+    pub fn run_scheduled(&mut self, step_sizes: &[f64], n_leapfrogs: &[i32], n_collect: usize) -> Result<Array3<T>, MmcmcError> {
+        if step_sizes.len() != n_leapfrogs.len() || n_collect > step_sizes.len() {
+            return Err(check(sys::MMCMC_ERR_INVALID_ARG).unwrap_err());
+        }
+        let n_discard = step_sizes.len() - n_collect;
+        let mut out = Array3::<T>::default((self.n_chains, n_collect, self.dim));
+        check(unsafe {
+            sys::mmcmc_hmc_run_scheduled(self.h, n_collect, n_discard, step_sizes.as_ptr(), n_leapfrogs.as_ptr(),
+                                         out.as_mut_ptr() as *mut c_void, 0, self.accept_counts.as_mut_ptr(), null_mut())
+        })?;
+        check(unsafe { sys::mmcmc_hmc_sync(self.h) })?;
+        Ok(out)
+    }
 }
 impl<T: GpuFloat> Drop for GpuHmc<T> {
     fn drop(&mut self) {
