@@ -35,7 +35,14 @@ extern "C" {
  *   out_host == NULL && accept_counts == NULL); mmcmc_nuts_set_repacking (100, measured slower, removed) stays removed.
  * 102 (round 6): + mmcmc_rtc_compiler_info; long-chain diagnostics take N1 = ceil(n/2 / 1024) residues (any count).
  * Later additions that keep 102 (a binding probes them with dlsym): mmcmc_hmc_set_step_size, mmcmc_hmc_set_n_leapfrog,
- *   mmcmc_hmc_params, mmcmc_hmc_set_state, mmcmc_hmc_run_scheduled.
+ *   mmcmc_hmc_params, mmcmc_hmc_set_state, mmcmc_hmc_run_scheduled; settable chain state and stream position
+ *   ("chain state and stream position" below): mmcmc_mh_set_proposal_std, mmcmc_mh_params, mmcmc_mh_set_state,
+ *   mmcmc_nuts_set_state, mmcmc_nuts_set_adapt_state, mmcmc_nuts_params, mmcmc_nuts_set_target_accept_p,
+ *   mmcmc_mh_discrete_set_state, mmcmc_gibbs_mixture_set_state, mmcmc_{mh,hmc,nuts,mh_discrete,gibbs_mixture}_stream_position,
+ *   mmcmc_{mh,hmc,nuts,mh_discrete,gibbs_mixture}_set_iteration, mmcmc_{mh,hmc,nuts}_group_set_state,
+ *   mmcmc_{mh,hmc,nuts}_group_stream_position, mmcmc_{mh,hmc,nuts}_group_set_iteration, mmcmc_{mh,hmc,nuts}_group_params,
+ *   mmcmc_hmc_group_set_step_size, mmcmc_hmc_group_set_n_leapfrog, mmcmc_mh_group_set_proposal_std,
+ *   mmcmc_nuts_group_adapt_state, mmcmc_nuts_group_set_adapt_state, mmcmc_nuts_group_set_target_accept_p.
  * A binding checks mmcmc_version() >= the version it was generated from (rust/mini-mcmc-hip: assert_abi, in every constructor). */
 #define MMCMC_VERSION 102 /* 0.1.2 */
 
@@ -595,6 +602,71 @@ int mmcmc_gibbs_mixture_run(mmcmc_gibbs_mixture *h, size_t n_collect, size_t n_d
 int mmcmc_gibbs_mixture_state(mmcmc_gibbs_mixture *h, double *out);             /* host [n_chains, 2] */
 int mmcmc_gibbs_mixture_sync(mmcmc_gibbs_mixture *h);
 int mmcmc_gibbs_mixture_destroy(mmcmc_gibbs_mixture *h);
+
+/* ---- chain state and stream position: checkpoint and resume ------------------------------------------------------
+ * The engine's noise is a function of (seed, global chain id, iteration) alone, so a handle's future is fixed by its
+ * positions, seed, chain offset, iteration counter and sampler fields, plus NUTS's per-chain adaptation records.  Each
+ * can be read and set below; a handle given all of another's continues exactly as that one would, bit for bit (samples,
+ * states, accept counts, adaptation), in another process or on another number of devices.  Additive to 102.
+ * Every setter makes its constructor's checks, leaves the handle unchanged when they fail, applies from the next
+ * transition on and touches nothing else (not the seed, chain offset or iteration unless that is what it sets).
+ *   mh_set_proposal_std: Sampler::scale of MH (metropolis_hastings.rs:101-109 `pub proposal`), finite and > 0 as in
+ *     mmcmc_mh_create; mmcmc_mh_params reads it.  mh_set_state / nuts_set_state: [n_chains, dim] of the handle's dtype (NUTS:
+ *     the mode's tensor type), host or device memory, ordered as mmcmc_hmc_set_state.
+ *   nuts_set_adapt_state: the exact inverse of mmcmc_nuts_adapt_state, host [n_chains, 4] doubles = epsilon, epsilon_bar,
+ *     h_bar, mu.  Every value finite (also in the mode's scalar type), epsilon > 0 or exactly the sentinel -1 (not yet
+ *     searched, nuts.rs:415-433).  Round trips are bit-exact in every mode (f32 through f64 is exact).  Ordered behind
+ *     every queued run of the device.  mmcmc_nuts_params reads target_accept_p and max_depth;
+ *     nuts_set_target_accept_p makes mmcmc_nuts_create's check (0 < p < 1).
+ *   mh_discrete_set_state: host [n_chains] i32; gibbs_mixture_set_state: host [n_chains, 2] f64 (behind every queued run).
+ *   *_stream_position: seed, chain offset and iteration (the next transition's index; NUTS: self.m, which the adaptation
+ *     also reads against n_discard); any pointer may be NULL.  *_set_iteration refuses values >= 2^32, the limit every run
+ *     already keeps.
+ * Not state: the accept counts (per run) and NUTS's leapfrog counts and depth histogram (cumulative diagnostics); the
+ * lane-group records of NUTS variants 1..3 (every transition writes its record before reading it) and the compaction
+ * level and pilot of variant 3 (they never change a result); the kernel variant and iters_per_launch (results identical).
+ * Groups fan out to their shards: set_state takes the global host [n_chains, dim] and copies each shard's rows on that
+ * shard's stream, behind its queued asynchronous runs; _stream_position gives the group's first global chain
+ * (mmcmc_*_group_set_chain_offset) and the shards' common iteration; the NUTS group's adaptation is global [n_chains, 4].
+ * The group field setters check their argument once, so no shard changes unless every shard does.  On a broken group
+ * (MMCMC_ERR_GROUP_BROKEN above) every setter and _stream_position return MMCMC_ERR_GROUP_BROKEN. */
+int mmcmc_mh_set_proposal_std(mmcmc_mh *h, double std);
+int mmcmc_mh_params(mmcmc_mh *h, double *std);
+int mmcmc_mh_set_state(mmcmc_mh *h, const void *x, int is_device, void *stream);
+int mmcmc_nuts_set_state(mmcmc_nuts *h, const void *x, int is_device, void *stream);
+int mmcmc_nuts_set_adapt_state(mmcmc_nuts *h, const double *in);
+int mmcmc_nuts_params(mmcmc_nuts *h, double *target_accept_p, int *max_depth);
+int mmcmc_nuts_set_target_accept_p(mmcmc_nuts *h, double target_accept_p);
+int mmcmc_mh_discrete_set_state(mmcmc_mh_discrete *h, const int32_t *x);
+int mmcmc_gibbs_mixture_set_state(mmcmc_gibbs_mixture *h, const double *x);
+int mmcmc_mh_stream_position(mmcmc_mh *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration);
+int mmcmc_hmc_stream_position(mmcmc_hmc *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration);
+int mmcmc_nuts_stream_position(mmcmc_nuts *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration);
+int mmcmc_mh_discrete_stream_position(mmcmc_mh_discrete *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration);
+int mmcmc_gibbs_mixture_stream_position(mmcmc_gibbs_mixture *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration);
+int mmcmc_mh_set_iteration(mmcmc_mh *h, uint64_t iteration);
+int mmcmc_hmc_set_iteration(mmcmc_hmc *h, uint64_t iteration);
+int mmcmc_nuts_set_iteration(mmcmc_nuts *h, uint64_t iteration);
+int mmcmc_mh_discrete_set_iteration(mmcmc_mh_discrete *h, uint64_t iteration);
+int mmcmc_gibbs_mixture_set_iteration(mmcmc_gibbs_mixture *h, uint64_t iteration);
+int mmcmc_hmc_group_set_state(mmcmc_hmc_group *g, const void *in);
+int mmcmc_mh_group_set_state(mmcmc_mh_group *g, const void *in);
+int mmcmc_nuts_group_set_state(mmcmc_nuts_group *g, const void *in);
+int mmcmc_hmc_group_set_step_size(mmcmc_hmc_group *g, double step_size);
+int mmcmc_hmc_group_set_n_leapfrog(mmcmc_hmc_group *g, int n_leapfrog);
+int mmcmc_hmc_group_params(mmcmc_hmc_group *g, double *step_size, int *n_leapfrog);
+int mmcmc_mh_group_set_proposal_std(mmcmc_mh_group *g, double std);
+int mmcmc_mh_group_params(mmcmc_mh_group *g, double *std);
+int mmcmc_nuts_group_adapt_state(mmcmc_nuts_group *g, double *out);
+int mmcmc_nuts_group_set_adapt_state(mmcmc_nuts_group *g, const double *in);
+int mmcmc_nuts_group_params(mmcmc_nuts_group *g, double *target_accept_p, int *max_depth);
+int mmcmc_nuts_group_set_target_accept_p(mmcmc_nuts_group *g, double target_accept_p);
+int mmcmc_hmc_group_stream_position(mmcmc_hmc_group *g, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration);
+int mmcmc_mh_group_stream_position(mmcmc_mh_group *g, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration);
+int mmcmc_nuts_group_stream_position(mmcmc_nuts_group *g, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration);
+int mmcmc_hmc_group_set_iteration(mmcmc_hmc_group *g, uint64_t iteration);
+int mmcmc_mh_group_set_iteration(mmcmc_mh_group *g, uint64_t iteration);
+int mmcmc_nuts_group_set_iteration(mmcmc_nuts_group *g, uint64_t iteration);
 
 /* ---- sample sink: io/csv.rs:47-69 save_csv -- header `chain,observation,dim_0,...`, one record per (chain,
  *      observation), values in Rust `Display` formatting (shortest round-trip, no exponent).  sample: HOST

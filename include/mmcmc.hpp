@@ -55,6 +55,11 @@ template <class T> std::vector<T> init_with_seed(size_t n, size_t d, uint64_t se
 }
 template <class T> std::vector<T> init_det(size_t n, size_t d) { return init_with_seed<T>(n, d, 42); }
 
+/* what keys a handle's next transition besides its positions (include/mmcmc.h: chain state and stream position) */
+struct StreamPosition {
+    uint64_t seed = 0, chain_offset = 0, iteration = 0;
+};
+
 /* ---- distributions ---- */
 struct Target {
     mmcmc_target_desc d{};
@@ -255,6 +260,42 @@ template <class T> class MetropolisHastings {
     }
     size_t n_chains() const { return n_chains_; }
     size_t dim() const { return dim_; }
+    /* the reference's public fields (metropolis_hastings.rs:101-109): from the next transition on */
+    MetropolisHastings &set_proposal_std(double std)
+    {
+        check(mmcmc_mh_set_proposal_std(h_, std), "mmcmc_mh_set_proposal_std");
+        return *this;
+    }
+    double proposal_std()
+    {
+        double std = 0;
+        check(mmcmc_mh_params(h_, &std), "mmcmc_mh_params");
+        return std;
+    }
+    std::vector<T> positions()
+    {
+        std::vector<T> out(n_chains_ * dim_);
+        check(mmcmc_mh_state(h_, out.data()), "mmcmc_mh_state");
+        return out;
+    }
+    MetropolisHastings &set_positions(const std::vector<T> &positions)
+    {
+        if (positions.size() != n_chains_ * dim_)
+            throw Error(MMCMC_ERR_SHAPE, "MetropolisHastings::set_positions");
+        check(mmcmc_mh_set_state(h_, positions.data(), 0, nullptr), "mmcmc_mh_set_state");
+        return *this;
+    }
+    StreamPosition stream_position()
+    {
+        StreamPosition p;
+        check(mmcmc_mh_stream_position(h_, &p.seed, &p.chain_offset, &p.iteration), "mmcmc_mh_stream_position");
+        return p;
+    }
+    MetropolisHastings &set_iteration(uint64_t iteration)
+    {
+        check(mmcmc_mh_set_iteration(h_, iteration), "mmcmc_mh_set_iteration");
+        return *this;
+    }
     /* ChainRunner::run_progress (core.rs:208-360): cb(user, done, total, p_accept, max_rhat) after every `every` transitions */
     ProgressResult<T> run_progress(size_t n_collect, size_t n_discard, size_t every = 0, mmcmc_progress_fn cb = nullptr,
                                    void *user = nullptr)
@@ -351,6 +392,17 @@ template <class T> class HMC {
         check(mmcmc_hmc_set_state(h_, positions.data(), 0, nullptr), "mmcmc_hmc_set_state");
         return *this;
     }
+    StreamPosition stream_position()
+    {
+        StreamPosition p;
+        check(mmcmc_hmc_stream_position(h_, &p.seed, &p.chain_offset, &p.iteration), "mmcmc_hmc_stream_position");
+        return p;
+    }
+    HMC &set_iteration(uint64_t iteration)
+    {
+        check(mmcmc_hmc_set_iteration(h_, iteration), "mmcmc_hmc_set_iteration");
+        return *this;
+    }
     /* transition k uses (step_sizes[k], n_leapfrogs[k]), the first size - n_collect are discarded: the loop
      * set_step_size; set_n_leapfrog; step() bit for bit, in one call */
     std::vector<T> run_scheduled(const std::vector<double> &step_sizes, const std::vector<int32_t> &n_leapfrogs, size_t n_collect)
@@ -419,6 +471,41 @@ template <class T> class HMCGroup {
         check(mmcmc_hmc_group_run_async(g_, n_collect, n_discard), "mmcmc_hmc_group_run_async");
     }
     void sync() { check(mmcmc_hmc_group_sync(g_), "mmcmc_hmc_group_sync"); }
+    /* global [n_chains, dim], split across the shards; behind the runs queued on each shard's stream */
+    HMCGroup &set_positions(const std::vector<T> &positions)
+    {
+        if (positions.size() != n_chains_ * dim_)
+            throw Error(MMCMC_ERR_SHAPE, "HMCGroup::set_positions");
+        check(mmcmc_hmc_group_set_state(g_, positions.data()), "mmcmc_hmc_group_set_state");
+        return *this;
+    }
+    std::vector<T> positions()
+    {
+        std::vector<T> out(n_chains_ * dim_);
+        check(mmcmc_hmc_group_state(g_, out.data()), "mmcmc_hmc_group_state");
+        return out;
+    }
+    HMCGroup &set_step_size(double step_size)
+    {
+        check(mmcmc_hmc_group_set_step_size(g_, step_size), "mmcmc_hmc_group_set_step_size");
+        return *this;
+    }
+    HMCGroup &set_n_leapfrog(int n_leapfrog)
+    {
+        check(mmcmc_hmc_group_set_n_leapfrog(g_, n_leapfrog), "mmcmc_hmc_group_set_n_leapfrog");
+        return *this;
+    }
+    StreamPosition stream_position()
+    {
+        StreamPosition p;
+        check(mmcmc_hmc_group_stream_position(g_, &p.seed, &p.chain_offset, &p.iteration), "mmcmc_hmc_group_stream_position");
+        return p;
+    }
+    HMCGroup &set_iteration(uint64_t iteration)
+    {
+        check(mmcmc_hmc_group_set_iteration(g_, iteration), "mmcmc_hmc_group_set_iteration");
+        return *this;
+    }
     /* how the diagnostics will travel (1 RCCL, 0 host by design, < 0 host as a fallback), known from construction on */
     int exchange() const
     {
@@ -455,6 +542,45 @@ template <class T> class NUTS {
     NUTS &set_seed(uint64_t s)
     {
         check(mmcmc_nuts_seed(h_, s), "mmcmc_nuts_seed");
+        return *this;
+    }
+    /* NUTSChain's public state (nuts.rs:361-386): position [n_chains, dim] and the adaptation records [n_chains, 4] =
+     * epsilon, epsilon_bar, h_bar, mu; from the next run on */
+    std::vector<float> positions()
+    {
+        std::vector<float> out(n_chains_ * dim_);
+        check(mmcmc_nuts_state(h_, out.data()), "mmcmc_nuts_state");
+        return out;
+    }
+    NUTS &set_positions(const std::vector<float> &positions)
+    {
+        if (positions.size() != n_chains_ * dim_)
+            throw Error(MMCMC_ERR_SHAPE, "NUTS::set_positions");
+        check(mmcmc_nuts_set_state(h_, positions.data(), 0, nullptr), "mmcmc_nuts_set_state");
+        return *this;
+    }
+    std::vector<double> adapt_state()
+    {
+        std::vector<double> out(n_chains_ * 4);
+        check(mmcmc_nuts_adapt_state(h_, out.data()), "mmcmc_nuts_adapt_state");
+        return out;
+    }
+    NUTS &set_adapt_state(const std::vector<double> &adapt)
+    {
+        if (adapt.size() != n_chains_ * 4)
+            throw Error(MMCMC_ERR_SHAPE, "NUTS::set_adapt_state");
+        check(mmcmc_nuts_set_adapt_state(h_, adapt.data()), "mmcmc_nuts_set_adapt_state");
+        return *this;
+    }
+    StreamPosition stream_position()
+    {
+        StreamPosition p;
+        check(mmcmc_nuts_stream_position(h_, &p.seed, &p.chain_offset, &p.iteration), "mmcmc_nuts_stream_position");
+        return p;
+    }
+    NUTS &set_iteration(uint64_t iteration)
+    {
+        check(mmcmc_nuts_set_iteration(h_, iteration), "mmcmc_nuts_set_iteration");
         return *this;
     }
     /* NUTS::run -> [n_chains, n_collect, dim] (f32, the backend's element type) */
@@ -501,6 +627,45 @@ template <class T> class NUTSGroup {
         check(mmcmc_nuts_group_seed(g_, s), "mmcmc_nuts_group_seed");
         return *this;
     }
+    /* NUTSChain's public state (nuts.rs:361-386): position [n_chains, dim] and the adaptation records [n_chains, 4] =
+     * epsilon, epsilon_bar, h_bar, mu; from the next run on */
+    std::vector<float> positions()
+    {
+        std::vector<float> out(n_chains_ * dim_);
+        check(mmcmc_nuts_group_state(g_, out.data()), "mmcmc_nuts_group_state");
+        return out;
+    }
+    NUTSGroup &set_positions(const std::vector<float> &positions)
+    {
+        if (positions.size() != n_chains_ * dim_)
+            throw Error(MMCMC_ERR_SHAPE, "NUTSGroup::set_positions");
+        check(mmcmc_nuts_group_set_state(g_, positions.data()), "mmcmc_nuts_group_set_state");
+        return *this;
+    }
+    std::vector<double> adapt_state()
+    {
+        std::vector<double> out(n_chains_ * 4);
+        check(mmcmc_nuts_group_adapt_state(g_, out.data()), "mmcmc_nuts_group_adapt_state");
+        return out;
+    }
+    NUTSGroup &set_adapt_state(const std::vector<double> &adapt)
+    {
+        if (adapt.size() != n_chains_ * 4)
+            throw Error(MMCMC_ERR_SHAPE, "NUTSGroup::set_adapt_state");
+        check(mmcmc_nuts_group_set_adapt_state(g_, adapt.data()), "mmcmc_nuts_group_set_adapt_state");
+        return *this;
+    }
+    StreamPosition stream_position()
+    {
+        StreamPosition p;
+        check(mmcmc_nuts_group_stream_position(g_, &p.seed, &p.chain_offset, &p.iteration), "mmcmc_nuts_group_stream_position");
+        return p;
+    }
+    NUTSGroup &set_iteration(uint64_t iteration)
+    {
+        check(mmcmc_nuts_group_set_iteration(g_, iteration), "mmcmc_nuts_group_set_iteration");
+        return *this;
+    }
     std::vector<float> run(size_t n_collect, size_t n_discard)
     {
         std::vector<float> out(n_chains_ * n_collect * dim_);
@@ -535,6 +700,45 @@ class NUTS64 {
     NUTS64 &set_seed(uint64_t s)
     {
         check(mmcmc_nuts_seed(h_, s), "mmcmc_nuts_seed");
+        return *this;
+    }
+    /* NUTSChain's public state (nuts.rs:361-386): position [n_chains, dim] and the adaptation records [n_chains, 4] =
+     * epsilon, epsilon_bar, h_bar, mu; from the next run on */
+    std::vector<double> positions()
+    {
+        std::vector<double> out(n_chains_ * dim_);
+        check(mmcmc_nuts_state(h_, out.data()), "mmcmc_nuts_state");
+        return out;
+    }
+    NUTS64 &set_positions(const std::vector<double> &positions)
+    {
+        if (positions.size() != n_chains_ * dim_)
+            throw Error(MMCMC_ERR_SHAPE, "NUTS64::set_positions");
+        check(mmcmc_nuts_set_state(h_, positions.data(), 0, nullptr), "mmcmc_nuts_set_state");
+        return *this;
+    }
+    std::vector<double> adapt_state()
+    {
+        std::vector<double> out(n_chains_ * 4);
+        check(mmcmc_nuts_adapt_state(h_, out.data()), "mmcmc_nuts_adapt_state");
+        return out;
+    }
+    NUTS64 &set_adapt_state(const std::vector<double> &adapt)
+    {
+        if (adapt.size() != n_chains_ * 4)
+            throw Error(MMCMC_ERR_SHAPE, "NUTS64::set_adapt_state");
+        check(mmcmc_nuts_set_adapt_state(h_, adapt.data()), "mmcmc_nuts_set_adapt_state");
+        return *this;
+    }
+    StreamPosition stream_position()
+    {
+        StreamPosition p;
+        check(mmcmc_nuts_stream_position(h_, &p.seed, &p.chain_offset, &p.iteration), "mmcmc_nuts_stream_position");
+        return p;
+    }
+    NUTS64 &set_iteration(uint64_t iteration)
+    {
+        check(mmcmc_nuts_set_iteration(h_, iteration), "mmcmc_nuts_set_iteration");
         return *this;
     }
     NUTS64 &set_max_depth(int d)
@@ -591,6 +795,25 @@ class DiscreteMetropolisHastings {
         check(mmcmc_mh_discrete_seed(h_, s), "mmcmc_mh_discrete_seed");
         return *this;
     }
+    /* MHMarkovChain::current_state of every chain [n_chains]: from the next run on */
+    DiscreteMetropolisHastings &set_state(const std::vector<int32_t> &states)
+    {
+        if (states.size() != n_chains_)
+            throw Error(MMCMC_ERR_SHAPE, "DiscreteMetropolisHastings::set_state");
+        check(mmcmc_mh_discrete_set_state(h_, states.data()), "mmcmc_mh_discrete_set_state");
+        return *this;
+    }
+    StreamPosition stream_position()
+    {
+        StreamPosition p;
+        check(mmcmc_mh_discrete_stream_position(h_, &p.seed, &p.chain_offset, &p.iteration), "mmcmc_mh_discrete_stream_position");
+        return p;
+    }
+    DiscreteMetropolisHastings &set_iteration(uint64_t iteration)
+    {
+        check(mmcmc_mh_discrete_set_iteration(h_, iteration), "mmcmc_mh_discrete_set_iteration");
+        return *this;
+    }
     std::vector<int32_t> run(size_t n_collect, size_t n_discard)
     {
         std::vector<int32_t> out(n_chains_ * n_collect);
@@ -624,6 +847,25 @@ class GibbsMixtureSampler {
     GibbsMixtureSampler &set_seed(uint64_t s)
     {
         check(mmcmc_gibbs_mixture_seed(h_, s), "mmcmc_gibbs_mixture_seed");
+        return *this;
+    }
+    /* GibbsMarkovChain::current_state of every chain [n_chains, 2]: from the next run on */
+    GibbsMixtureSampler &set_state(const std::vector<double> &states)
+    {
+        if (states.size() != n_chains_ * 2)
+            throw Error(MMCMC_ERR_SHAPE, "GibbsMixtureSampler::set_state");
+        check(mmcmc_gibbs_mixture_set_state(h_, states.data()), "mmcmc_gibbs_mixture_set_state");
+        return *this;
+    }
+    StreamPosition stream_position()
+    {
+        StreamPosition p;
+        check(mmcmc_gibbs_mixture_stream_position(h_, &p.seed, &p.chain_offset, &p.iteration), "mmcmc_gibbs_mixture_stream_position");
+        return p;
+    }
+    GibbsMixtureSampler &set_iteration(uint64_t iteration)
+    {
+        check(mmcmc_gibbs_mixture_set_iteration(h_, iteration), "mmcmc_gibbs_mixture_set_iteration");
         return *this;
     }
     std::vector<double> run(size_t n_collect, size_t n_discard)

@@ -213,6 +213,44 @@ SIGNATURES = {
     "mmcmc_nuts_group_stream_timer": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_float)]),
     "mmcmc_nuts_group_exchange": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mmcmc_nuts_group_destroy": (C.c_int, [_vp]),
+    # settable chain state and stream position (include/mmcmc.h: "chain state and stream position")
+    "mmcmc_mh_set_proposal_std": (C.c_int, [_vp, C.c_double]),
+    "mmcmc_mh_params": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_mh_set_state": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+    "mmcmc_nuts_set_state": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+    "mmcmc_nuts_set_adapt_state": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_nuts_params": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "mmcmc_nuts_set_target_accept_p": (C.c_int, [_vp, C.c_double]),
+    "mmcmc_mh_discrete_set_state": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    "mmcmc_gibbs_mixture_set_state": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_hmc_group_set_state": (C.c_int, [_vp, _vp]),
+    "mmcmc_mh_group_set_state": (C.c_int, [_vp, _vp]),
+    "mmcmc_nuts_group_set_state": (C.c_int, [_vp, _vp]),
+    "mmcmc_hmc_group_set_step_size": (C.c_int, [_vp, C.c_double]),
+    "mmcmc_hmc_group_set_n_leapfrog": (C.c_int, [_vp, C.c_int]),
+    "mmcmc_hmc_group_params": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "mmcmc_mh_group_set_proposal_std": (C.c_int, [_vp, C.c_double]),
+    "mmcmc_mh_group_params": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_nuts_group_adapt_state": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_nuts_group_set_adapt_state": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_nuts_group_params": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "mmcmc_nuts_group_set_target_accept_p": (C.c_int, [_vp, C.c_double]),
+    "mmcmc_mh_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mmcmc_mh_set_iteration": (C.c_int, [_vp, C.c_uint64]),
+    "mmcmc_hmc_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mmcmc_hmc_set_iteration": (C.c_int, [_vp, C.c_uint64]),
+    "mmcmc_nuts_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mmcmc_nuts_set_iteration": (C.c_int, [_vp, C.c_uint64]),
+    "mmcmc_mh_discrete_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mmcmc_mh_discrete_set_iteration": (C.c_int, [_vp, C.c_uint64]),
+    "mmcmc_gibbs_mixture_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mmcmc_gibbs_mixture_set_iteration": (C.c_int, [_vp, C.c_uint64]),
+    "mmcmc_hmc_group_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mmcmc_hmc_group_set_iteration": (C.c_int, [_vp, C.c_uint64]),
+    "mmcmc_mh_group_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mmcmc_mh_group_set_iteration": (C.c_int, [_vp, C.c_uint64]),
+    "mmcmc_nuts_group_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mmcmc_nuts_group_set_iteration": (C.c_int, [_vp, C.c_uint64]),
 }
 
 

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .checkpoint import Checkpointable
 
 
 def init_with_seed(n: int, d: int, seed: int, dtype=np.float64) -> np.ndarray:
@@ -29,7 +30,7 @@ def init(n: int, d: int, dtype=np.float64) -> np.ndarray:
     return init_with_seed(n, d, seed, dtype)
 
 
-class _Sampler:
+class _Sampler(Checkpointable):
     """Shared plumbing of the GPU samplers: owns one C-ABI handle."""
 
     _prefix = ""
@@ -110,6 +111,26 @@ class _Sampler:
         out = np.empty((self.n_chains, self.dim), dtype=self.dtype)
         L.check(self._fn("state")(self._h, out.ctypes.data), "state")
         return out
+
+    def _set_state(self, x) -> None:
+        """[n_chains, D] of the handle's dtype: a numpy array, or a contiguous torch tensor on the handle's device (copied on
+        torch's current stream, like run(to="torch"))."""
+        name = f"mmcmc_{self._prefix}_set_state"
+        if type(x).__module__.startswith("torch"):
+            import torch
+
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            if (x.dtype != tdt or tuple(x.shape) != (self.n_chains, self.dim) or not x.is_contiguous() or x.device.type != "cuda"
+                    or x.device.index != self.device):
+                raise ValueError(f"positions: a contiguous {tdt} tensor [{self.n_chains}, {self.dim}] on cuda:{self.device}")
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            L.check(self._fn("set_state")(self._h, C.c_void_p(x.data_ptr()), 1, C.c_void_p(stream)), name)
+            return
+        a = np.asarray(x)
+        if a.shape != (self.n_chains, self.dim):
+            raise ValueError(f"positions: shape {a.shape} != ({self.n_chains}, {self.dim})")
+        a = np.ascontiguousarray(a, dtype=self.dtype)
+        L.check(self._fn("set_state")(self._h, a.ctypes.data, 0, None), name)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

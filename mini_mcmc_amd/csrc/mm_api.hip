@@ -782,6 +782,53 @@ int sampler_state(Sampler *s, void *out)
     return MMCMC_OK;
 }
 
+/* positions [n_chains, dim] of the handle's dtype from host memory (is_device = 0: copied before the call returns) or from
+ * device memory on the handle's device, ordered on `stream` (NULL: the handle's own) like a run.  Every kernel variant
+ * derives log-density and gradient from the state at launch: nothing else to invalidate. */
+int sampler_set_state(Sampler *s, const void *positions, int is_device, void *stream)
+{
+    if (!s || !positions)
+        return MMCMC_ERR_INVALID_ARG;
+    DeviceGuard g(s->device);
+    if (is_device) {
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, positions) != hipSuccess) {
+            (void)hipGetLastError();
+            return MMCMC_ERR_INVALID_ARG;
+        }
+        if ((attr.type != hipMemoryTypeDevice && !attr.isManaged) || attr.device != s->device)
+            return MMCMC_ERR_INVALID_ARG;
+    }
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    MM_HIP(hipMemcpyAsync(s->d_state, positions, s->n_chains * (size_t)s->dim * s->esize(),
+                          is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if (!is_device)
+        MM_HIP(hipStreamSynchronize(st)); /* the caller's host buffer is free again on return */
+    return MMCMC_OK;
+}
+
+/* what keys the handle's future noise besides its positions: (seed, chain offset, iteration) */
+int sampler_stream_position(const Sampler *s, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration)
+{
+    if (seed)
+        *seed = s->seed;
+    if (chain_offset)
+        *chain_offset = s->chain_offset;
+    if (iteration)
+        *iteration = s->iter;
+    return MMCMC_OK;
+}
+
+/* the next transition's iteration index; run() refuses to pass 2^32, so a counter there could never run again.  A run
+ * already enqueued took its first iteration as a kernel argument: nothing on the device to order behind */
+int sampler_set_iteration(Sampler *s, uint64_t iteration)
+{
+    if (iteration >= (1ull << 32))
+        return MMCMC_ERR_INVALID_ARG;
+    s->iter = iteration;
+    return MMCMC_OK;
+}
+
 int sampler_sync(Sampler *s)
 {
     if (!s)
@@ -1167,6 +1214,35 @@ int mmcmc_mh_shape(mmcmc_mh *h, size_t *n_chains, int *dim, int *dtype, int *dev
 int mmcmc_mh_state(mmcmc_mh *h, void *out) { return h ? sampler_state(h->s, out) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_mh_sync(mmcmc_mh *h) { return h ? sampler_sync(h->s) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_mh_timing(mmcmc_mh *h, mmcmc_timing *t) { return h ? sampler_timing(h->s, t) : MMCMC_ERR_INVALID_ARG; }
+/* the reference's public fields (metropolis_hastings.rs:101-109: pub proposal, pub current_state) -- from the next
+ * transition on; seed, chain offset and iteration untouched */
+int mmcmc_mh_set_proposal_std(mmcmc_mh *h, double std)
+{
+    if (!h || !(std > 0.0) || !std::isfinite(std)) /* mmcmc_mh_create's check */
+        return MMCMC_ERR_INVALID_ARG;
+    h->s->scale = std;
+    return MMCMC_OK;
+}
+int mmcmc_mh_params(mmcmc_mh *h, double *std)
+{
+    if (!h)
+        return MMCMC_ERR_INVALID_ARG;
+    if (std)
+        *std = h->s->scale;
+    return MMCMC_OK;
+}
+int mmcmc_mh_set_state(mmcmc_mh *h, const void *x, int is_device, void *stream)
+{
+    return h ? sampler_set_state(h->s, x, is_device, stream) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_mh_stream_position(mmcmc_mh *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration)
+{
+    return h ? sampler_stream_position(h->s, seed, chain_offset, iteration) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_mh_set_iteration(mmcmc_mh *h, uint64_t iteration)
+{
+    return h ? sampler_set_iteration(h->s, iteration) : MMCMC_ERR_INVALID_ARG;
+}
 int mmcmc_mh_destroy(mmcmc_mh *h)
 {
     if (!h)
@@ -1263,26 +1339,15 @@ int mmcmc_hmc_params(mmcmc_hmc *h, double *step_size, int *n_leapfrog)
 }
 int mmcmc_hmc_set_state(mmcmc_hmc *h, const void *positions, int is_device, void *stream)
 {
-    if (!h || !positions)
-        return MMCMC_ERR_INVALID_ARG;
-    Sampler *s = h->s;
-    DeviceGuard g(s->device);
-    if (is_device) {
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, positions) != hipSuccess) {
-            (void)hipGetLastError();
-            return MMCMC_ERR_INVALID_ARG;
-        }
-        if ((attr.type != hipMemoryTypeDevice && !attr.isManaged) || attr.device != s->device)
-            return MMCMC_ERR_INVALID_ARG;
-    }
-    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-    /* every kernel variant derives log-density and gradient from the state at launch: nothing else to invalidate */
-    MM_HIP(hipMemcpyAsync(s->d_state, positions, s->n_chains * (size_t)s->dim * s->esize(),
-                          is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    if (!is_device)
-        MM_HIP(hipStreamSynchronize(st)); /* the caller's host buffer is free again on return */
-    return MMCMC_OK;
+    return h ? sampler_set_state(h->s, positions, is_device, stream) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_hmc_stream_position(mmcmc_hmc *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration)
+{
+    return h ? sampler_stream_position(h->s, seed, chain_offset, iteration) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_hmc_set_iteration(mmcmc_hmc *h, uint64_t iteration)
+{
+    return h ? sampler_set_iteration(h->s, iteration) : MMCMC_ERR_INVALID_ARG;
 }
 int mmcmc_hmc_run_scheduled(mmcmc_hmc *h, size_t n_collect, size_t n_discard, const double *step_sizes,
                             const int32_t *n_leapfrogs, void *out, int out_is_device, uint64_t *accept_counts, void *stream)

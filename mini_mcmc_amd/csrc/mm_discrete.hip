@@ -547,6 +547,39 @@ int mmcmc_mh_discrete_state(mmcmc_mh_discrete *h, int32_t *out)
     return MMCMC_OK;
 }
 
+/* MHMarkovChain::current_state (metropolis_hastings.rs:101-109) of every chain from host [n_chains]; any integer is
+ * accepted, as by mmcmc_mh_discrete_create (a state outside a table has log-density -inf).  Behind every queued run */
+int mmcmc_mh_discrete_set_state(mmcmc_mh_discrete *h, const int32_t *x)
+{
+    if (!h || !x)
+        return MMCMC_ERR_INVALID_ARG;
+    DevGuard g(h->device);
+    MM_HIP(hipDeviceSynchronize());
+    MM_HIP(hipMemcpy(h->d_state, x, h->n_chains * sizeof(int32_t), hipMemcpyHostToDevice));
+    return MMCMC_OK;
+}
+
+int mmcmc_mh_discrete_stream_position(mmcmc_mh_discrete *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration)
+{
+    if (!h)
+        return MMCMC_ERR_INVALID_ARG;
+    if (seed)
+        *seed = h->seed;
+    if (chain_offset)
+        *chain_offset = h->chain_offset;
+    if (iteration)
+        *iteration = h->iter;
+    return MMCMC_OK;
+}
+
+int mmcmc_mh_discrete_set_iteration(mmcmc_mh_discrete *h, uint64_t iteration)
+{
+    if (!h || iteration >= (1ull << 32))
+        return MMCMC_ERR_INVALID_ARG;
+    h->iter = (uint32_t)iteration;
+    return MMCMC_OK;
+}
+
 int mmcmc_mh_discrete_accept_counts(mmcmc_mh_discrete *h, uint64_t *out)
 {
     if (!h || !out)

@@ -331,6 +331,38 @@ int mmcmc_gibbs_mixture_state(mmcmc_gibbs_mixture *h, double *out)
     return MMCMC_OK;
 }
 
+/* GibbsMarkovChain::current_state (gibbs.rs:34-46) of every chain from host [n_chains, 2].  Behind every queued run */
+int mmcmc_gibbs_mixture_set_state(mmcmc_gibbs_mixture *h, const double *x)
+{
+    if (!h || !x)
+        return MMCMC_ERR_INVALID_ARG;
+    DevGuard g(h->device);
+    MM_HIP(hipDeviceSynchronize());
+    MM_HIP(hipMemcpy(h->d_state, x, h->n_chains * 2 * sizeof(double), hipMemcpyHostToDevice));
+    return MMCMC_OK;
+}
+
+int mmcmc_gibbs_mixture_stream_position(mmcmc_gibbs_mixture *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration)
+{
+    if (!h)
+        return MMCMC_ERR_INVALID_ARG;
+    if (seed)
+        *seed = h->seed;
+    if (chain_offset)
+        *chain_offset = h->chain_offset;
+    if (iteration)
+        *iteration = h->iter;
+    return MMCMC_OK;
+}
+
+int mmcmc_gibbs_mixture_set_iteration(mmcmc_gibbs_mixture *h, uint64_t iteration)
+{
+    if (!h || iteration >= (1ull << 32))
+        return MMCMC_ERR_INVALID_ARG;
+    h->iter = (uint32_t)iteration;
+    return MMCMC_OK;
+}
+
 int mmcmc_gibbs_mixture_sync(mmcmc_gibbs_mixture *h)
 {
     if (!h)

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
@@ -558,6 +559,55 @@ int group_state(Group *g, void *out)
     });
 }
 
+/* positions [n_chains, dim] (host; NUTS: of the tensor type) split across the shards; each copy is ordered behind the
+ * runs queued on its shard's stream and done when the call returns */
+int group_set_state(Group *g, const void *in)
+{
+    if (!g || !in)
+        return MMCMC_ERR_INVALID_ARG;
+    if (g->broken)
+        return MMCMC_ERR_GROUP_BROKEN;
+    const size_t esz = g->esize();
+    return for_each_shard(g, [&](Shard &s, int) -> int {
+        const void *p = (const char *)in + s.first * (size_t)g->dim * esz;
+        return g->sampler == 2 ? mmcmc_nuts_set_state(s.nuts, p, 0, s.stream)
+               : g->sampler    ? mmcmc_hmc_set_state(s.hmc, p, 0, s.stream)
+                               : mmcmc_mh_set_state(s.mh, p, 0, s.stream);
+    });
+}
+
+/* (seed, first global chain, iteration): the shards share seed and iteration; their chain offsets follow from the first */
+int group_stream_position(Group *g, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration)
+{
+    if (!g)
+        return MMCMC_ERR_INVALID_ARG;
+    if (g->broken)
+        return MMCMC_ERR_GROUP_BROKEN; /* the shards stand at different iterations */
+    const Shard &s = g->sh[0];
+    const int rc = g->sampler == 2 ? mmcmc_nuts_stream_position(s.nuts, seed, nullptr, iteration)
+                   : g->sampler    ? mmcmc_hmc_stream_position(s.hmc, seed, nullptr, iteration)
+                                   : mmcmc_mh_stream_position(s.mh, seed, nullptr, iteration);
+    if (rc == MMCMC_OK && first_global_chain)
+        *first_global_chain = g->user_offset;
+    return rc;
+}
+
+int group_set_iteration(Group *g, uint64_t iteration)
+{
+    if (!g || iteration >= (1ull << 32))
+        return MMCMC_ERR_INVALID_ARG;
+    if (g->broken)
+        return MMCMC_ERR_GROUP_BROKEN;
+    for (Shard &s : g->sh) {
+        const int rc = g->sampler == 2 ? mmcmc_nuts_set_iteration(s.nuts, iteration)
+                       : g->sampler    ? mmcmc_hmc_set_iteration(s.hmc, iteration)
+                                       : mmcmc_mh_set_iteration(s.mh, iteration);
+        if (rc != MMCMC_OK)
+            return rc;
+    }
+    return MMCMC_OK;
+}
+
 /* split-R-hat / ESS of the last run's sample (stats.rs:416-423) over ALL devices' chains */
 int group_split_rhat_ess(Group *g, float *rhat, float *ess, int *used_rccl)
 {
@@ -765,6 +815,45 @@ int mmcmc_hmc_group_run_async(mmcmc_hmc_group *h, size_t n_collect, size_t n_dis
 }
 int mmcmc_hmc_group_stats_phases(mmcmc_hmc_group *h, double *ms3) { return h ? group_stats_phases(h->g, ms3) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_hmc_group_state(mmcmc_hmc_group *h, void *out) { return h ? group_state(h->g, out) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_hmc_group_set_state(mmcmc_hmc_group *h, const void *in) { return h ? group_set_state(h->g, in) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_hmc_group_set_step_size(mmcmc_hmc_group *h, double step_size)
+{
+    if (!h || !(step_size > 0.0) || !std::isfinite(step_size)) /* checked once: no shard changes unless all do */
+        return MMCMC_ERR_INVALID_ARG;
+    if (h->g->broken)
+        return MMCMC_ERR_GROUP_BROKEN;
+    for (Shard &s : h->g->sh) {
+        const int rc = mmcmc_hmc_set_step_size(s.hmc, step_size);
+        if (rc != MMCMC_OK)
+            return rc;
+    }
+    return MMCMC_OK;
+}
+int mmcmc_hmc_group_set_n_leapfrog(mmcmc_hmc_group *h, int n_leapfrog)
+{
+    if (!h || n_leapfrog < 0)
+        return MMCMC_ERR_INVALID_ARG;
+    if (h->g->broken)
+        return MMCMC_ERR_GROUP_BROKEN;
+    for (Shard &s : h->g->sh) {
+        const int rc = mmcmc_hmc_set_n_leapfrog(s.hmc, n_leapfrog);
+        if (rc != MMCMC_OK)
+            return rc;
+    }
+    return MMCMC_OK;
+}
+int mmcmc_hmc_group_params(mmcmc_hmc_group *h, double *step_size, int *n_leapfrog)
+{
+    return h ? mmcmc_hmc_params(h->g->sh[0].hmc, step_size, n_leapfrog) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_hmc_group_stream_position(mmcmc_hmc_group *h, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration)
+{
+    return h ? group_stream_position(h->g, seed, first_global_chain, iteration) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_hmc_group_set_iteration(mmcmc_hmc_group *h, uint64_t iteration)
+{
+    return h ? group_set_iteration(h->g, iteration) : MMCMC_ERR_INVALID_ARG;
+}
 int mmcmc_hmc_group_split_rhat_mean_ess(mmcmc_hmc_group *h, float *rhat, float *ess, int *used_rccl)
 {
     return h ? group_split_rhat_ess(h->g, rhat, ess, used_rccl) : MMCMC_ERR_INVALID_ARG;
@@ -831,6 +920,29 @@ int mmcmc_mh_group_run_async(mmcmc_mh_group *h, size_t n_collect, size_t n_disca
 }
 int mmcmc_mh_group_stats_phases(mmcmc_mh_group *h, double *ms3) { return h ? group_stats_phases(h->g, ms3) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_mh_group_state(mmcmc_mh_group *h, void *out) { return h ? group_state(h->g, out) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_mh_group_set_state(mmcmc_mh_group *h, const void *in) { return h ? group_set_state(h->g, in) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_mh_group_set_proposal_std(mmcmc_mh_group *h, double std)
+{
+    if (!h || !(std > 0.0) || !std::isfinite(std))
+        return MMCMC_ERR_INVALID_ARG;
+    if (h->g->broken)
+        return MMCMC_ERR_GROUP_BROKEN;
+    for (Shard &s : h->g->sh) {
+        const int rc = mmcmc_mh_set_proposal_std(s.mh, std);
+        if (rc != MMCMC_OK)
+            return rc;
+    }
+    return MMCMC_OK;
+}
+int mmcmc_mh_group_params(mmcmc_mh_group *h, double *std) { return h ? mmcmc_mh_params(h->g->sh[0].mh, std) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_mh_group_stream_position(mmcmc_mh_group *h, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration)
+{
+    return h ? group_stream_position(h->g, seed, first_global_chain, iteration) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_mh_group_set_iteration(mmcmc_mh_group *h, uint64_t iteration)
+{
+    return h ? group_set_iteration(h->g, iteration) : MMCMC_ERR_INVALID_ARG;
+}
 int mmcmc_mh_group_split_rhat_mean_ess(mmcmc_mh_group *h, float *rhat, float *ess, int *used_rccl)
 {
     return h ? group_split_rhat_ess(h->g, rhat, ess, used_rccl) : MMCMC_ERR_INVALID_ARG;
@@ -900,6 +1012,56 @@ int mmcmc_nuts_group_leapfrog_counts(mmcmc_nuts_group *h, uint64_t *out)
     if (!h || !out)
         return MMCMC_ERR_INVALID_ARG;
     return for_each_shard(h->g, [&](Shard &s, int) -> int { return mmcmc_nuts_leapfrog_counts(s.nuts, out + s.first); });
+}
+int mmcmc_nuts_group_set_state(mmcmc_nuts_group *h, const void *in) { return h ? group_set_state(h->g, in) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_nuts_group_adapt_state(mmcmc_nuts_group *h, double *out)
+{
+    if (!h || !out)
+        return MMCMC_ERR_INVALID_ARG;
+    return for_each_shard(h->g, [&](Shard &s, int) -> int { return mmcmc_nuts_adapt_state(s.nuts, out + 4 * s.first); });
+}
+int mmcmc_nuts_group_set_adapt_state(mmcmc_nuts_group *h, const double *in)
+{
+    if (!h || !in)
+        return MMCMC_ERR_INVALID_ARG;
+    if (h->g->broken)
+        return MMCMC_ERR_GROUP_BROKEN;
+    /* mmcmc_nuts_set_adapt_state's checks on every row first: no shard changes unless all do */
+    int mode = 0;
+    (void)mmcmc_nuts_shape(h->g->sh[0].nuts, nullptr, nullptr, &mode, nullptr);
+    for (size_t i = 0; i < 4 * h->g->n_chains; ++i) {
+        const double v = in[i];
+        if (!std::isfinite(v) || (mode == 1 && !std::isfinite((float)v)))
+            return MMCMC_ERR_INVALID_ARG;
+        if (i % 4 == 0 && !((mode == 1 ? (double)(float)v : v) > 0.0) && v != -1.0)
+            return MMCMC_ERR_INVALID_ARG;
+    }
+    return for_each_shard(h->g, [&](Shard &s, int) -> int { return mmcmc_nuts_set_adapt_state(s.nuts, in + 4 * s.first); });
+}
+int mmcmc_nuts_group_params(mmcmc_nuts_group *h, double *target_accept_p, int *max_depth)
+{
+    return h ? mmcmc_nuts_params(h->g->sh[0].nuts, target_accept_p, max_depth) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_nuts_group_set_target_accept_p(mmcmc_nuts_group *h, double target_accept_p)
+{
+    if (!h || !(target_accept_p > 0.0 && target_accept_p < 1.0))
+        return MMCMC_ERR_INVALID_ARG;
+    if (h->g->broken)
+        return MMCMC_ERR_GROUP_BROKEN;
+    for (Shard &s : h->g->sh) {
+        const int rc = mmcmc_nuts_set_target_accept_p(s.nuts, target_accept_p);
+        if (rc != MMCMC_OK)
+            return rc;
+    }
+    return MMCMC_OK;
+}
+int mmcmc_nuts_group_stream_position(mmcmc_nuts_group *h, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration)
+{
+    return h ? group_stream_position(h->g, seed, first_global_chain, iteration) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_nuts_group_set_iteration(mmcmc_nuts_group *h, uint64_t iteration)
+{
+    return h ? group_set_iteration(h->g, iteration) : MMCMC_ERR_INVALID_ARG;
 }
 int mmcmc_nuts_group_split_rhat_mean_ess(mmcmc_nuts_group *h, float *rhat, float *ess, int *used_rccl)
 {

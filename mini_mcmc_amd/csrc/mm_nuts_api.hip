@@ -57,6 +57,8 @@ struct NutsBase {
     virtual int run(size_t n_collect, size_t n_discard, void *out, int out_is_device, int progress, void *stream) = 0;
     virtual int state(void *out) = 0;
     virtual int adapt_state(double *out) = 0;
+    virtual int set_state(const void *x, int is_device, void *stream) = 0;
+    virtual int set_adapt_state(const double *in) = 0;
     virtual int leapfrog_counts(uint64_t *out) = 0;
     virtual int depth_histogram(uint32_t *out) = 0;
     virtual int set_variant(int v) = 0;
@@ -722,6 +724,52 @@ template <class TT, class ST> struct Nuts : NutsBase {
         }
         return MMCMC_OK;
     }
+    /* positions [n_chains, dim] of the tensor type, host or device memory (as mmcmc_hmc_set_state).  Each run() starts
+     * with init_chain from the state and the adaptation records (nuts.rs:528-545); nothing else derives from them */
+    int set_state(const void *x, int is_device, void *stream_v) override
+    {
+        DevGuard g(device);
+        if (is_device) {
+            hipPointerAttribute_t attr{};
+            if (hipPointerGetAttributes(&attr, x) != hipSuccess) {
+                (void)hipGetLastError();
+                return MMCMC_ERR_INVALID_ARG;
+            }
+            if ((attr.type != hipMemoryTypeDevice && !attr.isManaged) || attr.device != device)
+                return MMCMC_ERR_INVALID_ARG;
+        }
+        hipStream_t st = stream_v ? (hipStream_t)stream_v : stream;
+        MM_HIP(hipMemcpyAsync(d_state, x, n_chains * (size_t)dim * sizeof(TT),
+                              is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        if (!is_device)
+            MM_HIP(hipStreamSynchronize(st));
+        return MMCMC_OK;
+    }
+    /* the inverse of adapt_state: [n_chains, 4] doubles = epsilon, epsilon_bar, h_bar, mu.  Every value finite in the
+     * scalar type, epsilon > 0 or exactly the sentinel -1 (no search yet, nuts.rs:415-433); nothing is written otherwise.
+     * The lane-group records (d_lg_rec) and the compaction level are not state: every transition writes its record before
+     * reading it, and the level never changes a result */
+    int set_adapt_state(const double *in) override
+    {
+        std::vector<mm_nuts_adapt<ST>> ad(n_chains);
+        for (size_t i = 0; i < n_chains; ++i) {
+            const double *r = in + 4 * i;
+            ad[i].epsilon = (ST)r[0];
+            ad[i].epsilon_bar = (ST)r[1];
+            ad[i].h_bar = (ST)r[2];
+            ad[i].mu = (ST)r[3];
+            const ST v[4] = {ad[i].epsilon, ad[i].epsilon_bar, ad[i].h_bar, ad[i].mu};
+            for (int q = 0; q < 4; ++q)
+                if (!std::isfinite(r[q]) || !std::isfinite(v[q]))
+                    return MMCMC_ERR_INVALID_ARG;
+            if (!(ad[i].epsilon > ST(0)) && r[0] != -1.0)
+                return MMCMC_ERR_INVALID_ARG;
+        }
+        DevGuard g(device);
+        MM_HIP(hipDeviceSynchronize()); /* behind every queued run, like adapt_state */
+        MM_HIP(hipMemcpy(d_adapt, ad.data(), n_chains * sizeof(mm_nuts_adapt<ST>), hipMemcpyHostToDevice));
+        return MMCMC_OK;
+    }
     int leapfrog_counts(uint64_t *out) override
     {
         DevGuard g(device);
@@ -943,6 +991,52 @@ int mmcmc_nuts_state(mmcmc_nuts *h, void *out) { return (h && out) ? h->p->state
 int mmcmc_nuts_adapt_state(mmcmc_nuts *h, double *out)
 {
     return (h && out) ? h->p->adapt_state(out) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_nuts_set_state(mmcmc_nuts *h, const void *x, int is_device, void *stream)
+{
+    return (h && x) ? h->p->set_state(x, is_device, stream) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_nuts_set_adapt_state(mmcmc_nuts *h, const double *in)
+{
+    return (h && in) ? h->p->set_adapt_state(in) : MMCMC_ERR_INVALID_ARG;
+}
+/* target_accept_p (fixed by mmcmc_nuts_create) and max_depth (mmcmc_nuts_set_max_depth); either pointer may be NULL */
+int mmcmc_nuts_params(mmcmc_nuts *h, double *target_accept_p, int *max_depth)
+{
+    if (!h)
+        return MMCMC_ERR_INVALID_ARG;
+    if (target_accept_p)
+        *target_accept_p = h->p->target_accept_p;
+    if (max_depth)
+        *max_depth = h->p->max_depth;
+    return MMCMC_OK;
+}
+int mmcmc_nuts_set_target_accept_p(mmcmc_nuts *h, double target_accept_p)
+{
+    if (!h || !(target_accept_p > 0.0 && target_accept_p < 1.0)) /* mmcmc_nuts_create's check */
+        return MMCMC_ERR_INVALID_ARG;
+    h->p->target_accept_p = target_accept_p;
+    return MMCMC_OK;
+}
+int mmcmc_nuts_stream_position(mmcmc_nuts *h, uint64_t *seed, uint64_t *chain_offset, uint64_t *iteration)
+{
+    if (!h)
+        return MMCMC_ERR_INVALID_ARG;
+    if (seed)
+        *seed = h->p->seed;
+    if (chain_offset)
+        *chain_offset = h->p->chain_offset;
+    if (iteration)
+        *iteration = h->p->m;
+    return MMCMC_OK;
+}
+/* self.m: the transitions taken so far -- it keys the noise and, against n_discard, the adaptation (nuts.rs:682) */
+int mmcmc_nuts_set_iteration(mmcmc_nuts *h, uint64_t iteration)
+{
+    if (!h || iteration >= (1ull << 32))
+        return MMCMC_ERR_INVALID_ARG;
+    h->p->m = (uint32_t)iteration;
+    return MMCMC_OK;
 }
 int mmcmc_nuts_leapfrog_counts(mmcmc_nuts *h, uint64_t *out)
 {

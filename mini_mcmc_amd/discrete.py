@@ -15,6 +15,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
+from .checkpoint import Checkpointable
 
 
 @dataclass(frozen=True)
@@ -67,11 +68,13 @@ class UserDiscreteModel:
         return self._params
 
 
-class DiscreteMetropolisHastings:
+class DiscreteMetropolisHastings(Checkpointable):
     """MetropolisHastings::new(target, proposal, initial_states) for the models above; one chain per GPU lane.
 
     initial_states: [n_chains] or [n_chains, 1] integers.  run(n_collect, n_discard) -> int32 [n_chains, n_collect, 1]
     (the reference's Array3<i32>); `accept_counts()` since creation."""
+
+    _cprefix = _ckpt_sampler = "mh_discrete"
 
     def __init__(self, model, initial_states, device: int = 0):
         init = np.ascontiguousarray(np.asarray(initial_states).reshape(-1), dtype=np.int32)
@@ -131,3 +134,15 @@ class DiscreteMetropolisHastings:
         out = np.empty(self.n_chains, dtype=np.uint64)
         L.check(L.lib().mmcmc_mh_discrete_accept_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))), "accept")
         return out
+
+    def set_state(self, x) -> "DiscreteMetropolisHastings":
+        """MHMarkovChain::current_state of every chain (metropolis_hastings.rs:101-109): [n_chains] (or [n_chains, 1])
+        integers; from the next run on."""
+        a = np.asarray(x)
+        if a.size != self.n_chains or a.shape not in ((self.n_chains,), (self.n_chains, 1)):
+            raise ValueError(f"state: shape {a.shape}, want ({self.n_chains},)")
+        if a.dtype.kind not in "iu" or (a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31)):
+            raise ValueError(f"state: {a.dtype} is not int32")
+        a = np.ascontiguousarray(a.reshape(-1), dtype=np.int32)
+        L.check(L.lib().mmcmc_mh_discrete_set_state(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), "mmcmc_mh_discrete_set_state")
+        return self

@@ -10,6 +10,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
+from .checkpoint import Checkpointable
 
 
 @dataclass(frozen=True)
@@ -26,9 +27,11 @@ class MixtureConditional:
         return [float(self.mu0), float(self.sigma0), float(self.mu1), float(self.sigma1), float(self.pi0)]
 
 
-class GibbsSampler:
+class GibbsSampler(Checkpointable):
     """GibbsSampler::new(conditional, initial_states) (gibbs.rs:139-157); one chain per GPU lane, states f64
     [n_chains, 2].  `set_seed` mirrors gibbs.rs:179-187, `run` is ChainRunner::run (core.rs:176-186)."""
+
+    _cprefix = _ckpt_sampler = "gibbs_mixture"
 
     def __init__(self, conditional: MixtureConditional, initial_states, device: int = 0):
         init = np.ascontiguousarray(initial_states, dtype=np.float64)
@@ -90,3 +93,12 @@ class GibbsSampler:
         out = np.empty((self.n_chains, 2), dtype=np.float64)
         L.check(L.lib().mmcmc_gibbs_mixture_state(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "state")
         return out
+
+    def set_state(self, x) -> "GibbsSampler":
+        """GibbsMarkovChain::current_state of every chain (gibbs.rs:34-46): [n_chains, 2] float64 [x, z]; from the next run on."""
+        a = np.asarray(x)
+        if a.shape != (self.n_chains, 2):
+            raise ValueError(f"state: shape {a.shape} != ({self.n_chains}, 2)")
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        L.check(L.lib().mmcmc_gibbs_mixture_set_state(self._h, a.ctypes.data_as(C.POINTER(C.c_double))), "mmcmc_gibbs_mixture_set_state")
+        return self

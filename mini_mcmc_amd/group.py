@@ -12,10 +12,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import checkpoint as K
 from .distributions import IsotropicGaussian, Target
 
 
-class _Group:
+class _Group(K.Checkpointable):
     _prefix = ""
 
     def _fn(self, name):
@@ -85,6 +86,24 @@ class _Group:
         L.check(self._fn("state")(self._h, out.ctypes.data), "group_state")
         return out
 
+    def set_positions(self, x):
+        """global positions [n_chains, dim] (NUTS: of the mode's tensor type), host memory, split across the shards; each
+        shard's copy is ordered behind the runs queued on its stream"""
+        a = np.asarray(x)
+        if a.shape != (self.n_chains, self.dim):
+            raise ValueError(f"positions: shape {a.shape} != ({self.n_chains}, {self.dim})")
+        a = np.ascontiguousarray(a, dtype=self.dtype)
+        L.check(self._fn("set_state")(self._h, a.ctypes.data), f"mmcmc_{self._prefix}_group_set_state")
+        return self
+
+    @property
+    def positions(self) -> np.ndarray:
+        return self.state()
+
+    @positions.setter
+    def positions(self, x) -> None:
+        self.set_positions(x)
+
     def split_rhat_mean_ess(self):
         """(rhat[dim], ess[dim]) of the last run's sample over the chains of ALL devices (stats.rs:416-423);
         `self.used_rccl` tells whether the statistics were exchanged by RCCL or through the host."""
@@ -114,6 +133,7 @@ class HMCGroup(_Group):
     """HMC::new(target, initial_positions, step_size, n_leapfrog) (hmc.rs:87-109) over `devices`."""
 
     _prefix = "hmc"
+    _cprefix, _ckpt_sampler = "hmc_group", "hmc"
 
     def __init__(self, target: Target, initial_positions, step_size: float, n_leapfrog: int, devices=(0,)):
         init = np.ascontiguousarray(initial_positions)
@@ -122,6 +142,7 @@ class HMCGroup(_Group):
         self.n_chains, self.dim = init.shape
         self.dtype = init.dtype.type
         self.devices = [int(d) for d in devices]
+        self.target = target
         dev = (C.c_int * len(self.devices))(*self.devices)
         self._h = C.c_void_p()
         d = target.desc()
@@ -132,6 +153,27 @@ class HMCGroup(_Group):
     def set_seed(self, seed: int) -> "HMCGroup":
         L.check(L.lib().mmcmc_hmc_group_seed(self._h, int(seed)), "mmcmc_hmc_group_seed")
         return self
+
+    def _params(self):
+        eps, n = C.c_double(), C.c_int()
+        L.check(L.lib().mmcmc_hmc_group_params(self._h, C.byref(eps), C.byref(n)), "mmcmc_hmc_group_params")
+        return eps.value, n.value
+
+    @property
+    def step_size(self) -> float:
+        return self._params()[0]
+
+    @step_size.setter
+    def step_size(self, eps: float) -> None:
+        L.check(L.lib().mmcmc_hmc_group_set_step_size(self._h, float(eps)), "mmcmc_hmc_group_set_step_size")
+
+    @property
+    def n_leapfrog(self) -> int:
+        return self._params()[1]
+
+    @n_leapfrog.setter
+    def n_leapfrog(self, n: int) -> None:
+        L.check(L.lib().mmcmc_hmc_group_set_n_leapfrog(self._h, int(n)), "mmcmc_hmc_group_set_n_leapfrog")
 
     def shards(self):
         """[(device, first_chain, n_chains, device pointer of the shard's sample [n_i, n_collect, dim])]"""
@@ -147,6 +189,7 @@ class MetropolisHastingsGroup(_Group):
     """MetropolisHastings::new(target, proposal, initial_states) (metropolis_hastings.rs:149-193) over `devices`."""
 
     _prefix = "mh"
+    _cprefix, _ckpt_sampler = "mh_group", "mh"
 
     def __init__(self, target: Target, proposal: IsotropicGaussian, initial_states, devices=(0,)):
         init = np.ascontiguousarray(initial_states)
@@ -155,6 +198,7 @@ class MetropolisHastingsGroup(_Group):
         self.n_chains, self.dim = init.shape
         self.dtype = init.dtype.type
         self.devices = [int(d) for d in devices]
+        self.target = target
         dev = (C.c_int * len(self.devices))(*self.devices)
         self._h = C.c_void_p()
         d, p = target.desc(), proposal.proposal_desc()
@@ -166,11 +210,22 @@ class MetropolisHastingsGroup(_Group):
         L.check(L.lib().mmcmc_mh_group_seed(self._h, int(seed)), "mmcmc_mh_group_seed")
         return self
 
+    @property
+    def proposal_std(self) -> float:
+        std = C.c_double()
+        L.check(L.lib().mmcmc_mh_group_params(self._h, C.byref(std)), "mmcmc_mh_group_params")
+        return std.value
+
+    @proposal_std.setter
+    def proposal_std(self, std: float) -> None:
+        L.check(L.lib().mmcmc_mh_group_set_proposal_std(self._h, float(std)), "mmcmc_mh_group_set_proposal_std")
+
 
 class NUTSGroup(_Group):
     """NUTS::new(target, initial_positions, target_accept_p) (nuts.rs:123-129) over `devices`; mode as in `nuts.NUTS`."""
 
     _prefix = "nuts"
+    _cprefix, _ckpt_sampler = "nuts_group", "nuts"
 
     def __init__(self, target: Target, initial_positions, target_accept_p: float, mode: int = 0, devices=(0,)):
         init = np.ascontiguousarray(initial_positions, dtype=np.float64)
@@ -178,6 +233,7 @@ class NUTSGroup(_Group):
         self.mode = int(mode)
         self.dtype = np.float64 if self.mode == 2 else np.float32
         self.devices = [int(d) for d in devices]
+        self.target = target
         dev = (C.c_int * len(self.devices))(*self.devices)
         self._h = C.c_void_p()
         d = target.desc()
@@ -205,3 +261,15 @@ class NUTSGroup(_Group):
         out = np.zeros(self.n_chains, dtype=np.uint64)
         L.check(L.lib().mmcmc_nuts_group_leapfrog_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))), "group_leapfrog_counts")
         return out
+
+    def adapt_state(self) -> dict:
+        """per-chain adaptation state of every shard, as NUTS.adapt_state()"""
+        a = K.adapt_array(self)
+        return dict(epsilon=a[:, 0], epsilon_bar=a[:, 1], h_bar=a[:, 2], mu=a[:, 3])
+
+    def set_adapt_state(self, adapt) -> "NUTSGroup":
+        """global [n_chains, 4] (or adapt_state()'s dict); every row is checked before any shard changes"""
+        if isinstance(adapt, dict):
+            adapt = np.stack([np.asarray(adapt[k], dtype=np.float64) for k in ("epsilon", "epsilon_bar", "h_bar", "mu")], axis=1)
+        K.set_adapt_array(self, adapt)
+        return self

@@ -14,6 +14,7 @@ class HMC(_Sampler):
     """HMC::new(target, initial_positions, step_size, n_leapfrog) (hmc.rs:87-109)."""
 
     _prefix = "hmc"
+    _cprefix = _ckpt_sampler = "hmc"
 
     def __init__(self, target: Target, initial_positions, step_size: float, n_leapfrog: int, device: int = 0):
         super().__init__()
@@ -88,21 +89,7 @@ class HMC(_Sampler):
     def positions(self, x) -> None:
         """[n_chains, D] of the handle's dtype: a numpy array, or a contiguous torch tensor on the handle's device (copied on
         torch's current stream, like run(to="torch"))."""
-        if type(x).__module__.startswith("torch"):
-            import torch
-
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            if (x.dtype != tdt or tuple(x.shape) != (self.n_chains, self.dim) or not x.is_contiguous() or x.device.type != "cuda"
-                    or x.device.index != self.device):
-                raise ValueError(f"positions: a contiguous {tdt} tensor [{self.n_chains}, {self.dim}] on cuda:{self.device}")
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            L.check(L.lib().mmcmc_hmc_set_state(self._h, C.c_void_p(x.data_ptr()), 1, C.c_void_p(stream)), "mmcmc_hmc_set_state")
-            return
-        a = np.asarray(x)
-        if a.shape != (self.n_chains, self.dim):
-            raise ValueError(f"positions: shape {a.shape} != ({self.n_chains}, {self.dim})")
-        a = np.ascontiguousarray(a, dtype=self.dtype)
-        L.check(L.lib().mmcmc_hmc_set_state(self._h, a.ctypes.data, 0, None), "mmcmc_hmc_set_state")
+        self._set_state(x)
 
     def run_scheduled(self, step_sizes, n_leapfrogs, n_collect: int, to: str = "numpy", accept_counts: bool = True):
         """Transition k of the run uses (step_sizes[k], n_leapfrogs[k]); the first len - n_collect transitions are discarded.

@@ -17,6 +17,7 @@ class MetropolisHastings(_Sampler):
     (core.rs:176-186).  The state element type follows `initial_states.dtype` (float32 / float64)."""
 
     _prefix = "mh"
+    _cprefix = _ckpt_sampler = "mh"
 
     def __init__(self, target: Target, proposal: IsotropicGaussian, initial_states, device: int = 0):
         super().__init__()
@@ -44,3 +45,27 @@ class MetropolisHastings(_Sampler):
     def seed(self, seed: int) -> "MetropolisHastings":
         L.check(L.lib().mmcmc_mh_seed(self._h, int(seed)), "mmcmc_mh_seed")
         return self
+
+    # The reference's public fields (metropolis_hastings.rs:101-109: pub proposal, pub current_state): setting one applies
+    # from the next transition on; seed, chain offset and iteration counter are untouched.
+    @property
+    def proposal_std(self) -> float:
+        """The isotropic proposal's standard deviation (IsotropicGaussian::std, what mmcmc_mh_create took)."""
+        std = C.c_double()
+        L.check(L.lib().mmcmc_mh_params(self._h, C.byref(std)), "mmcmc_mh_params")
+        return std.value
+
+    @proposal_std.setter
+    def proposal_std(self, std: float) -> None:
+        L.check(L.lib().mmcmc_mh_set_proposal_std(self._h, float(std)), "mmcmc_mh_set_proposal_std")
+
+    @property
+    def positions(self) -> np.ndarray:
+        """MHMarkovChain::current_state of every chain [n_chains, D]."""
+        return self.state()
+
+    @positions.setter
+    def positions(self, x) -> None:
+        """[n_chains, D] of the handle's dtype: a numpy array, or a contiguous torch tensor on the handle's device (copied on
+        torch's current stream, like run(to="torch"))."""
+        self._set_state(x)

@@ -6,15 +6,18 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import checkpoint as K
 from .distributions import IsotropicGaussian, Target
 
 
-class NUTS:
+class NUTS(K.Checkpointable):
     """NUTS::new(target, initial_positions, target_accept_p) (nuts.rs:123-129).
 
     mode 0: f32 tensors + f64 scalars (the reference's `NUTS<f64, Autodiff<NdArray>, _>`), 1: f32 + f32,
     2: f64 + f64.  `run(n_collect, n_discard)` keeps the reference's N-1-steps semantics; `run_progress` takes all
     N steps and returns (sample, RunStats) like nuts.rs:194-338 (without the terminal UI)."""
+
+    _cprefix = _ckpt_sampler = "nuts"
 
     def __init__(self, target: Target, initial_positions, target_accept_p: float, mode: int = 0, device: int = 0):
         init = np.ascontiguousarray(initial_positions, dtype=np.float64)
@@ -106,6 +109,53 @@ class NUTS:
         out = np.empty((self.n_chains, 4), dtype=np.float64)
         L.check(L.lib().mmcmc_nuts_adapt_state(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "adapt_state")
         return dict(epsilon=out[:, 0], epsilon_bar=out[:, 1], h_bar=out[:, 2], mu=out[:, 3])
+
+    # NUTSChain's public state (nuts.rs:361-386: pub position and the adaptation fields): from the next run on; seed, chain
+    # offset and iteration (self.m) untouched.
+    def set_positions(self, x) -> "NUTS":
+        """[n_chains, D] of the mode's tensor type (float32 for modes 0 / 1, float64 for mode 2): a numpy array, or a
+        contiguous torch tensor on the handle's device (copied on torch's current stream)."""
+        if type(x).__module__.startswith("torch"):
+            import torch
+
+            tdt = torch.float64 if self.mode == 2 else torch.float32
+            if (x.dtype != tdt or tuple(x.shape) != (self.n_chains, self.dim) or not x.is_contiguous() or x.device.type != "cuda"
+                    or x.device.index != self.device):
+                raise ValueError(f"positions: a contiguous {tdt} tensor [{self.n_chains}, {self.dim}] on cuda:{self.device}")
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            L.check(L.lib().mmcmc_nuts_set_state(self._h, C.c_void_p(x.data_ptr()), 1, C.c_void_p(stream)), "mmcmc_nuts_set_state")
+            return self
+        a = np.asarray(x)
+        if a.shape != (self.n_chains, self.dim):
+            raise ValueError(f"positions: shape {a.shape} != ({self.n_chains}, {self.dim})")
+        a = np.ascontiguousarray(a, dtype=self.dtype)
+        L.check(L.lib().mmcmc_nuts_set_state(self._h, a.ctypes.data, 0, None), "mmcmc_nuts_set_state")
+        return self
+
+    def set_adapt_state(self, adapt) -> "NUTS":
+        """The inverse of adapt_state(): its dict, or [n_chains, 4] = epsilon, epsilon_bar, h_bar, mu.  Finite values,
+        epsilon > 0 or the sentinel -1 (not yet searched)."""
+        if isinstance(adapt, dict):
+            adapt = np.stack([np.asarray(adapt[k], dtype=np.float64) for k in ("epsilon", "epsilon_bar", "h_bar", "mu")], axis=1)
+        K.set_adapt_array(self, adapt)
+        return self
+
+    def _params(self):
+        p, d = C.c_double(), C.c_int()
+        L.check(L.lib().mmcmc_nuts_params(self._h, C.byref(p), C.byref(d)), "mmcmc_nuts_params")
+        return p.value, d.value
+
+    @property
+    def target_accept_p(self) -> float:
+        return self._params()[0]
+
+    def set_target_accept_p(self, p: float) -> "NUTS":
+        L.check(L.lib().mmcmc_nuts_set_target_accept_p(self._h, float(p)), "mmcmc_nuts_set_target_accept_p")
+        return self
+
+    @property
+    def max_depth(self) -> int:
+        return self._params()[1]
 
     def leapfrog_counts(self) -> np.ndarray:
         out = np.zeros(self.n_chains, dtype=np.uint64)

@@ -583,3 +583,84 @@ pub fn register_proposal_source(name: &str, target_kind: i32, dim: usize, hip_so
     let st = unsafe { sys::mmcmc_proposal_register_source(n.as_ptr(), target_kind, dim as c_int, s.as_ptr(), &mut kind, log.as_mut_ptr(), log.len()) };
     if st == sys::MMCMC_OK { Ok(kind) } else { Err(unsafe { CStr::from_ptr(log.as_ptr()) }.to_string_lossy().into_owned()) }
 }
+
+/// What keys a handle's next transition besides its positions: `(seed, chain_offset, iteration)` (include/mmcmc.h,
+/// "chain state and stream position").  A handle given another's positions, fields and stream position (and, for NUTS,
+/// adaptation records) continues exactly as that one does.
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct StreamPosition {
+    pub seed: u64,
+    pub chain_offset: u64,
+    pub iteration: u64,
+}
+
+impl<T: GpuFloat> GpuMetropolisHastings<T> {
+    /// `chain.proposal = IsotropicGaussian::new(std)` (metropolis_hastings.rs:101-109, a public field): from the next transition on
+    pub fn set_proposal_std(&mut self, std: f64) -> Result<(), MmcmcError> {
+        check(unsafe { sys::mmcmc_mh_set_proposal_std(self.h, std) })
+    }
+    pub fn proposal_std(&self) -> Result<f64, MmcmcError> {
+        let mut std = 0.0;
+        check(unsafe { sys::mmcmc_mh_params(self.h, &mut std) })?;
+        Ok(std)
+    }
+    /// `chain.current_state = x` for every chain (metropolis_hastings.rs:101-109): `[n_chains, dim]`
+    pub fn set_positions(&mut self, positions: &Array2<T>) -> Result<(), MmcmcError> {
+        if positions.dim() != (self.n_chains, self.dim) {
+            return check(sys::MMCMC_ERR_SHAPE);
+        }
+        let owned = positions.as_standard_layout();
+        check(unsafe { sys::mmcmc_mh_set_state(self.h, owned.as_ptr() as *const c_void, 0, null_mut()) })
+    }
+    pub fn stream_position(&self) -> Result<StreamPosition, MmcmcError> {
+        let mut p = StreamPosition::default();
+        check(unsafe { sys::mmcmc_mh_stream_position(self.h, &mut p.seed, &mut p.chain_offset, &mut p.iteration) })?;
+        Ok(p)
+    }
+    pub fn set_iteration(&mut self, iteration: u64) -> Result<(), MmcmcError> {
+        check(unsafe { sys::mmcmc_mh_set_iteration(self.h, iteration) })
+    }
+}
+impl<T: GpuFloat> GpuHmc<T> {
+    pub fn stream_position(&self) -> Result<StreamPosition, MmcmcError> {
+        let mut p = StreamPosition::default();
+        check(unsafe { sys::mmcmc_hmc_stream_position(self.h, &mut p.seed, &mut p.chain_offset, &mut p.iteration) })?;
+        Ok(p)
+    }
+    pub fn set_iteration(&mut self, iteration: u64) -> Result<(), MmcmcError> {
+        check(unsafe { sys::mmcmc_hmc_set_iteration(self.h, iteration) })
+    }
+}
+impl GpuNuts {
+    /// `chain.position = x` for every chain (nuts.rs:361-370): `[n_chains, dim]` f32 (the backend's element type)
+    pub fn set_positions(&mut self, positions: &Array2<f32>) -> Result<(), MmcmcError> {
+        if positions.dim() != (self.n_chains, self.dim) {
+            return check(sys::MMCMC_ERR_SHAPE);
+        }
+        let owned = positions.as_standard_layout();
+        check(unsafe { sys::mmcmc_nuts_set_state(self.h, owned.as_ptr() as *const c_void, 0, null_mut()) })
+    }
+    /// the adaptation fields of every chain (nuts.rs:374-386): `[n_chains, 4]` = epsilon, epsilon_bar, h_bar, mu
+    pub fn adapt_state(&self) -> Result<Array2<f64>, MmcmcError> {
+        let mut out = Array2::<f64>::zeros((self.n_chains, 4));
+        check(unsafe { sys::mmcmc_nuts_adapt_state(self.h, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    /// the inverse of `adapt_state`: finite values, epsilon > 0 or the "not yet searched" sentinel -1
+    pub fn set_adapt_state(&mut self, adapt: &Array2<f64>) -> Result<(), MmcmcError> {
+        if adapt.dim() != (self.n_chains, 4) {
+            return check(sys::MMCMC_ERR_SHAPE);
+        }
+        let owned = adapt.as_standard_layout();
+        check(unsafe { sys::mmcmc_nuts_set_adapt_state(self.h, owned.as_ptr()) })
+    }
+    /// the iteration is `self.m` (the adaptation reads it against n_discard)
+    pub fn stream_position(&self) -> Result<StreamPosition, MmcmcError> {
+        let mut p = StreamPosition::default();
+        check(unsafe { sys::mmcmc_nuts_stream_position(self.h, &mut p.seed, &mut p.chain_offset, &mut p.iteration) })?;
+        Ok(p)
+    }
+    pub fn set_iteration(&mut self, iteration: u64) -> Result<(), MmcmcError> {
+        check(unsafe { sys::mmcmc_nuts_set_iteration(self.h, iteration) })
+    }
+}
