@@ -42,7 +42,8 @@ extern "C" {
  *   mmcmc_{mh,hmc,nuts,mh_discrete,gibbs_mixture}_set_iteration, mmcmc_{mh,hmc,nuts}_group_set_state,
  *   mmcmc_{mh,hmc,nuts}_group_stream_position, mmcmc_{mh,hmc,nuts}_group_set_iteration, mmcmc_{mh,hmc,nuts}_group_params,
  *   mmcmc_hmc_group_set_step_size, mmcmc_hmc_group_set_n_leapfrog, mmcmc_mh_group_set_proposal_std,
- *   mmcmc_nuts_group_adapt_state, mmcmc_nuts_group_set_adapt_state, mmcmc_nuts_group_set_target_accept_p.
+ *   mmcmc_nuts_group_adapt_state, mmcmc_nuts_group_set_adapt_state, mmcmc_nuts_group_set_target_accept_p;
+ *   rank-normalised diagnostics: mmcmc_rank_normalize, mmcmc_quantiles, mmcmc_rank_diagnostics.
  * A binding checks mmcmc_version() >= the version it was generated from (rust/mini-mcmc-hip: assert_abi, in every constructor). */
 #define MMCMC_VERSION 102 /* 0.1.2 */
 
@@ -482,6 +483,49 @@ int mmcmc_stats_set_direct_work_limit(uint64_t max_lag_products);
 int mmcmc_basic_stats_from(const float *data, size_t len, mmcmc_basic_stats *out);
 int mmcmc_run_stats_from(const void *sample, int sample_is_device, int dtype, size_t n_chains, size_t n, size_t dim,
                     mmcmc_run_stats *out, int device, void *stream);
+
+/* ---- rank-normalised diagnostics (csrc/mm_rank.hip; not in the reference) -----------------------------------------
+ * Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021): the mean-based split R-hat above cannot see chains that agree in
+ * location and differ in scale or tails, and a mean ESS says nothing about the 5 % / 95 % quantiles.  For sample
+ * [n_chains, n, dim] (device or host, dtype; cast to f32 first like RunStats::from, stats.rs:365; f64 input is ranked by its
+ * f32 casts), S = n_chains x n, every parameter on its own:
+ *   ranks       all S draws pooled; -0.0 == +0.0; equal values share the average of their 1-based positions;
+ *               rank2 = first + last position of the tie group = 2 x the average rank, exact in uint32
+ *   scores      z = Phi^-1((rank2 / 2 - 3/8) / (S + 1/4)) evaluated in f64 on the device, rounded once to f32
+ *   folded      the same for |x - med| (f32), med = the pooled median (quantile rule below, rounded to f32)
+ *   quantiles   numpy's default (type 7): h = (S - 1) p, j = floor(h), q = a + (h - j) (b - a) in f64 from the sorted f32
+ *               draws a, b at j, j + 1
+ *   rhat_bulk / rhat_folded   the CONVENTIONAL split R-hat sqrt(var+ / W) of z / of the folded z (the inverse of what
+ *               mmcmc_split_rhat_mean_ess reports, quirk Q7); rhat_rank = their maximum
+ *   ess_bulk    the library's split ESS of z;  ess_tail = min over q in {q05, q95} of the split ESS of the 0 / 1 indicator
+ *               I(x <= q).  "The library's split ESS" is exactly mmcmc_split_rhat_mean_ess (splitcat, the reference's
+ *               Geyer pairing, the AUTO kernel choice): the definitions are Vehtari et al.'s, the ESS estimator is the
+ *               reference's, so the figures are not promised to equal Stan's or ArviZ's digit for digit.
+ *   A parameter with any NaN draw gets NaN in every output and rank2 = 0; +-inf sort like numbers.  A constant parameter
+ *   goes through the pipeline as it is (NaN wherever 0 / 0 arises).
+ * The hot path is a stable LSD radix sort of (key, index) pairs, four 8-bit passes, hand-written for gfx950; results are a
+ * pure function of the input, bit-reproducible across runs, streams and devices.  The calls block: they return when the
+ * outputs are there.  Work memory: 16 x S bytes + histograms for the sort (one parameter at a time); _rank_diagnostics
+ * additionally two f32 arrays of the sample's shape.
+ * SINGLE DEVICE: ranks are global over chains, so a sample sharded over a device group has to be gathered first; the
+ * mmcmc_*_group handles have no rank diagnostics.
+ * Status: MMCMC_ERR_INVALID_ARG  NULL sample / z, a probability outside [0, 1], n_probs > 0 with NULL probs (or NULL output);
+ *         MMCMC_ERR_SHAPE        n_chains x n >= 2^31, dim >= 2^16, for _rank_diagnostics also n < 2 and every shape limit of
+ *                                mmcmc_split_rhat_mean_ess -- decided from the shape before anything is allocated;
+ *         MMCMC_ERR_NO_DEVICE    no device, like every compute entry point.
+ * These entry points are additive: MMCMC_VERSION stays 102. */
+/* z: f32 [n_chains, n, dim], device memory if z_is_device else host; rank2 (may be NULL): uint32, same shape, same place as z;
+ * folded != 0: the scores (and ranks) of |x - med| */
+int mmcmc_rank_normalize(const void *sample, int sample_is_device, int dtype, size_t n_chains, size_t n, size_t dim,
+                         int folded, float *z, int z_is_device, uint32_t *rank2, int device, void *stream);
+/* out: host [n_probs, dim] */
+int mmcmc_quantiles(const void *sample, int sample_is_device, int dtype, size_t n_chains, size_t n, size_t dim,
+                    const double *probs, size_t n_probs, double *out, int device, void *stream);
+/* every output host [dim] and nullable; rhat_parts [2, dim] = bulk, folded; ess_tail_parts [2, dim] = lower (q05), upper (q95);
+ * quantiles [n_probs, dim] when n_probs > 0 */
+int mmcmc_rank_diagnostics(const void *sample, int sample_is_device, int dtype, size_t n_chains, size_t n, size_t dim,
+                           float *rhat_rank, float *rhat_parts, float *ess_bulk, float *ess_tail, float *ess_tail_parts,
+                           const double *probs, size_t n_probs, double *quantiles, int device, void *stream);
 
 /* ---- running diagnostics: MultiChainTracker (stats.rs:189-306) -------------------------------------------------
  * What run_progress shows while sampling (hmc.rs:242-281: `p(accept)` and `max(rhat)` after every step).  The tracker

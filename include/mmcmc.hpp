@@ -147,6 +147,51 @@ inline std::pair<std::vector<float>, std::vector<float>> split_rhat_mean_ess(con
     return {rhat, ess};
 }
 
+/* Rank-normalised diagnostics (Vehtari et al. 2021; mmcmc.h "rank-normalised diagnostics"): host samples [chains, n, dim] */
+inline std::vector<float> rank_normalize(const std::vector<float> &sample, size_t chains, size_t n, size_t dim,
+                                         bool folded = false, std::vector<uint32_t> *rank2 = nullptr, int device = 0)
+{
+    std::vector<float> z(chains * n * dim);
+    if (rank2)
+        rank2->resize(z.size());
+    check(mmcmc_rank_normalize(sample.data(), 0, MMCMC_F32, chains, n, dim, folded ? 1 : 0, z.data(), 0,
+                               rank2 ? rank2->data() : nullptr, device, nullptr),
+          "mmcmc_rank_normalize");
+    return z;
+}
+/* [probs.size(), dim], numpy's default rule */
+inline std::vector<double> quantiles(const std::vector<float> &sample, size_t chains, size_t n, size_t dim,
+                                     const std::vector<double> &probs, int device = 0)
+{
+    std::vector<double> out(probs.size() * dim);
+    check(mmcmc_quantiles(sample.data(), 0, MMCMC_F32, chains, n, dim, probs.data(), probs.size(), out.data(), device, nullptr),
+          "mmcmc_quantiles");
+    return out;
+}
+struct RankDiagnostics {
+    std::vector<float> rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_tail_lower, ess_tail_upper;
+    std::vector<double> quantiles; /* [probs.size(), dim] */
+};
+inline RankDiagnostics rank_diagnostics(const std::vector<float> &sample, size_t chains, size_t n, size_t dim,
+                                        const std::vector<double> &probs = {0.05, 0.5, 0.95}, int device = 0)
+{
+    RankDiagnostics r;
+    std::vector<float> rparts(2 * dim), tparts(2 * dim);
+    r.rhat.resize(dim);
+    r.ess_bulk.resize(dim);
+    r.ess_tail.resize(dim);
+    r.quantiles.resize(probs.size() * dim);
+    check(mmcmc_rank_diagnostics(sample.data(), 0, MMCMC_F32, chains, n, dim, r.rhat.data(), rparts.data(), r.ess_bulk.data(),
+                                 r.ess_tail.data(), tparts.data(), probs.empty() ? nullptr : probs.data(), probs.size(),
+                                 probs.empty() ? nullptr : r.quantiles.data(), device, nullptr),
+          "mmcmc_rank_diagnostics");
+    r.rhat_bulk.assign(rparts.begin(), rparts.begin() + dim);
+    r.rhat_folded.assign(rparts.begin() + dim, rparts.end());
+    r.ess_tail_lower.assign(tparts.begin(), tparts.begin() + dim);
+    r.ess_tail_upper.assign(tparts.begin() + dim, tparts.end());
+    return r;
+}
+
 /* MultiChainTracker (stats.rs:189-306): step() takes host states [n_chains, k, dim] */
 class MultiChainTracker {
     mmcmc_tracker *h_ = nullptr;

@@ -251,6 +251,14 @@ SIGNATURES = {
     "mmcmc_mh_group_set_iteration": (C.c_int, [_vp, C.c_uint64]),
     "mmcmc_nuts_group_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mmcmc_nuts_group_set_iteration": (C.c_int, [_vp, C.c_uint64]),
+    # rank-normalised diagnostics (csrc/mm_rank.hip)
+    "mmcmc_rank_normalize": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _vp, C.c_int, _vp,
+                                       C.c_int, _vp]),
+    "mmcmc_quantiles": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), C.c_size_t,
+                                  C.POINTER(C.c_double), C.c_int, _vp]),
+    "mmcmc_rank_diagnostics": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_double), C.c_int, _vp]),
 }
 
 

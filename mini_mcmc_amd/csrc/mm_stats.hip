@@ -2120,6 +2120,12 @@ static bool stats_bins_fit(size_t n, size_t dim)
     return (uint64_t)dim * N < (1ull << 32);
 }
 
+/* the same test for mm_rank.hip, whose entry points run mmcmc_split_rhat_mean_ess on arrays of the sample's shape (mm_rank.h) */
+bool mm_stats_shape_fits(size_t n, size_t dim)
+{
+    return stats_bins_fit(n, dim);
+}
+
 /* floats of device workspace stats_partials_impl wants behind `slabs_ws` */
 static size_t stats_ws_floats(size_t n_chains, size_t n, size_t dim, unsigned int n_parts, int device)
 {

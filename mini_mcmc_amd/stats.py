@@ -115,6 +115,147 @@ def run_stats(sample) -> RunStats:
     return RunStats(basic_stats("ESS", ess), basic_stats("Split R-hat", rhat))
 
 
+_dp = C.POINTER(C.c_double)
+
+
+@dataclass
+class RankDiagnostics:
+    """Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021) per parameter.  rhat = max(rhat_bulk, rhat_folded), the
+    CONVENTIONAL sqrt(var+ / W) (what `standard_split_rhat` reports, not the reference's inverse) of the rank-normalised
+    draws and of the rank-normalised folded draws |x - median|; ess_bulk the split ESS of the former; ess_tail =
+    min(ess_tail_lower, ess_tail_upper), the split ESS of I(x <= q05) and I(x <= q95); quantiles [len(probs), params] float64."""
+    rhat: np.ndarray
+    rhat_bulk: np.ndarray
+    rhat_folded: np.ndarray
+    ess_bulk: np.ndarray
+    ess_tail: np.ndarray
+    ess_tail_lower: np.ndarray
+    ess_tail_upper: np.ndarray
+    quantiles: np.ndarray
+
+
+@dataclass
+class Summary:
+    """The per-parameter table of `summary`: pooled mean and sd, the Monte-Carlo standard error of the mean, the 5 / 50 / 95 %
+    quantiles and the rank-normalised diagnostics."""
+    names: list
+    mean: np.ndarray
+    sd: np.ndarray
+    mcse_mean: np.ndarray
+    q5: np.ndarray
+    q50: np.ndarray
+    q95: np.ndarray
+    rhat: np.ndarray
+    ess_bulk: np.ndarray
+    ess_tail: np.ndarray
+
+    def __str__(self):
+        cols = ("mean", "sd", "mcse_mean", "q5", "q50", "q95", "rhat", "ess_bulk", "ess_tail")
+        w = max([len(str(n)) for n in self.names] + [5])
+        lines = [" " * w + "".join(f"{c:>12}" for c in cols)]
+        for j, name in enumerate(self.names):
+            cells = "".join(f"{float(getattr(self, c)[j]):12.4f}" if c == "rhat" else f"{float(getattr(self, c)[j]):12.4g}"
+                            for c in cols)
+            lines.append(f"{str(name):<{w}}{cells}")
+        return "\n".join(lines)
+
+
+def _shape3(shape):
+    if len(shape) != 3:
+        raise ValueError("sample must be [chains, n, params]")
+    return shape
+
+
+def rank_normalize(sample, folded: bool = False, return_ranks: bool = False):
+    """Normal scores of the pooled, tie-averaged ranks of every parameter: sample [chains, n, params] (numpy, or a torch
+    tensor in HBM; ranked as f32) -> z float32 of the same shape, z = Phi^-1((rank - 3/8) / (S + 1/4)), S = chains x n.
+    folded: of |x - median| instead.  return_ranks: also rank2 = 2 x the average rank, exact integers.  A device tensor in
+    gives device tensors out (rank2 as int64); a parameter with a NaN draw is NaN throughout (rank2 0)."""
+    ptr, is_dev, code, shape, dev, stream, keep = _sample_args(sample)
+    c, n, p = _shape3(shape)
+    if is_dev:
+        import torch
+
+        z = torch.empty((c, n, p), dtype=torch.float32, device=keep.device)
+        r = torch.empty((c, n, p), dtype=torch.int32, device=keep.device) if return_ranks else None
+        zp, rp = z.data_ptr(), (r.data_ptr() if return_ranks else None)
+    else:
+        z = np.empty((c, n, p), dtype=np.float32)
+        r = np.empty((c, n, p), dtype=np.uint32) if return_ranks else None
+        zp, rp = z.ctypes.data, (r.ctypes.data if return_ranks else None)
+    st = L.lib().mmcmc_rank_normalize(ptr, is_dev, code, c, n, p, int(bool(folded)), zp, is_dev, rp, dev, stream)
+    L.check(st, "mmcmc_rank_normalize")
+    if not return_ranks:
+        return z
+    if is_dev:
+        r = r.to(torch.int64) & 0xFFFFFFFF  # the uint32 the library wrote
+    return z, r
+
+
+def quantiles(sample, probs):
+    """numpy's default ("type 7") quantiles of the pooled f32 draws of every parameter, interpolated in float64:
+    sample [chains, n, params] -> float64 [len(probs), params]."""
+    ptr, is_dev, code, shape, dev, stream, keep = _sample_args(sample)
+    c, n, p = _shape3(shape)
+    pr = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
+    out = np.empty((pr.size, p), dtype=np.float64)
+    st = L.lib().mmcmc_quantiles(ptr, is_dev, code, c, n, p, pr.ctypes.data_as(_dp), pr.size, out.ctypes.data_as(_dp), dev,
+                                 stream)
+    L.check(st, "mmcmc_quantiles")
+    return out
+
+
+def rank_diagnostics(sample, probs=(0.05, 0.5, 0.95)) -> RankDiagnostics:
+    """Rank-normalised split R-hat (bulk and folded), bulk and tail ESS and quantiles of sample [chains, n, params] (numpy, or a
+    torch tensor in HBM), computed on the device.  The definitions are Vehtari et al.'s (2021); the ESS estimator behind them
+    is this library's split ESS -- `split_rhat_mean_ess` on the transformed draws: splitcat, the reference's Geyer pairing,
+    the "auto" kernel choice -- so the figures are NOT promised to equal Stan's or ArviZ's digit for digit."""
+    ptr, is_dev, code, shape, dev, stream, keep = _sample_args(sample)
+    c, n, p = _shape3(shape)
+    pr = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
+    rhat = np.empty(p, dtype=np.float32)
+    parts = np.empty((2, p), dtype=np.float32)
+    bulk = np.empty(p, dtype=np.float32)
+    tail = np.empty(p, dtype=np.float32)
+    tparts = np.empty((2, p), dtype=np.float32)
+    q = np.empty((pr.size, p), dtype=np.float64)
+    st = L.lib().mmcmc_rank_diagnostics(ptr, is_dev, code, c, n, p, rhat.ctypes.data_as(_fp), parts.ctypes.data_as(_fp),
+                                        bulk.ctypes.data_as(_fp), tail.ctypes.data_as(_fp), tparts.ctypes.data_as(_fp),
+                                        pr.ctypes.data_as(_dp) if pr.size else None, pr.size,
+                                        q.ctypes.data_as(_dp) if pr.size else None, dev, stream)
+    L.check(st, "mmcmc_rank_diagnostics")
+    return RankDiagnostics(rhat, parts[0].copy(), parts[1].copy(), bulk, tail, tparts[0].copy(), tparts[1].copy(), q)
+
+
+def summary(sample, names=None) -> Summary:
+    """The table practitioners read, per parameter: mean and sd (pooled over the split half-chains' sufficient statistics,
+    finished in float64), mcse_mean = sd / sqrt(ESS of the raw draws, today's `split_rhat_mean_ess`), q5 / q50 / q95 and the
+    rank-normalised R-hat, bulk ESS and tail ESS of `rank_diagnostics`."""
+    import torch
+
+    t = sample if isinstance(sample, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sample))
+    if not t.is_cuda:
+        if not torch.cuda.is_available():
+            raise L.MmcmcError(L.ERR_NO_DEVICE, "summary")
+        t = t.cuda()
+    c, n, p = _shape3(tuple(t.shape))
+    names = [f"x{j}" for j in range(p)] if names is None else list(names)
+    if len(names) != p:
+        raise ValueError(f"{p} parameters, {len(names)} names")
+    means, ssq, _ = stats_partials(t)
+    mu = means.reshape(-1, p).double().cpu().numpy()
+    sq = ssq.reshape(-1, p).double().cpu().numpy()
+    m = n // 2
+    mean = mu.mean(axis=0)
+    total = sq.sum(axis=0) + m * ((mu - mean) ** 2).sum(axis=0)
+    sd = np.sqrt(total / (mu.shape[0] * m - 1))
+    _, ess_mean = split_rhat_mean_ess(t)
+    r = rank_diagnostics(t, (0.05, 0.5, 0.95))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mcse = sd / np.sqrt(ess_mean.astype(np.float64))
+    return Summary(names, mean, sd, mcse, r.quantiles[0], r.quantiles[1], r.quantiles[2], r.rhat, r.ess_bulk, r.ess_tail)
+
+
 def stats_partials(sample):
     """Device-side sufficient statistics of the local chains (torch CUDA tensor in, torch CUDA tensors out):
     means [2, C, D], ssq [2, C, D] (splitcat order: half index first) and acov_sum [n/2, D]."""

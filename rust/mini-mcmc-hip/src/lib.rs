@@ -356,6 +356,48 @@ pub fn split_rhat_mean_ess(sample: ArrayView3<f32>) -> Result<(Array1<f32>, Arra
     Ok((rhat, ess))
 }
 
+/// Normal scores of the pooled, tie-averaged ranks of every parameter (Vehtari et al. 2021); `folded`: of `|x - median|`.
+pub fn rank_normalize(sample: ArrayView3<f32>, folded: bool) -> Result<Array3<f32>, MmcmcError> {
+    let (c, n, p) = sample.dim();
+    let owned = sample.as_standard_layout();
+    let mut z = Array3::<f32>::zeros((c, n, p));
+    check(unsafe {
+        sys::mmcmc_rank_normalize(owned.as_ptr() as *const c_void, 0, sys::MMCMC_F32, c, n, p, folded as c_int, z.as_mut_ptr(), 0, null_mut(), 0, null_mut())
+    })?;
+    Ok(z)
+}
+
+/// numpy's default quantiles of the pooled draws of every parameter, row-major `[probs.len(), params]`.
+pub fn quantiles(sample: ArrayView3<f32>, probs: &[f64]) -> Result<Vec<f64>, MmcmcError> {
+    let (c, n, p) = sample.dim();
+    let owned = sample.as_standard_layout();
+    let mut out = vec![0f64; probs.len() * p];
+    check(unsafe {
+        sys::mmcmc_quantiles(owned.as_ptr() as *const c_void, 0, sys::MMCMC_F32, c, n, p, probs.as_ptr(), probs.len(), out.as_mut_ptr(), 0, null_mut())
+    })?;
+    Ok(out)
+}
+
+/// Rank-normalised split R-hat (conventional, `sqrt(var+ / W)`), bulk ESS and tail ESS per parameter.
+pub struct RankDiagnostics {
+    pub rhat: Array1<f32>,
+    pub rhat_parts: Vec<f32>,
+    pub ess_bulk: Array1<f32>,
+    pub ess_tail: Array1<f32>,
+    pub ess_tail_parts: Vec<f32>,
+}
+
+pub fn rank_diagnostics(sample: ArrayView3<f32>) -> Result<RankDiagnostics, MmcmcError> {
+    let (c, n, p) = sample.dim();
+    let owned = sample.as_standard_layout();
+    let (mut rhat, mut bulk, mut tail) = (Array1::<f32>::zeros(p), Array1::<f32>::zeros(p), Array1::<f32>::zeros(p));
+    let (mut rparts, mut tparts) = (vec![0f32; 2 * p], vec![0f32; 2 * p]);
+    check(unsafe {
+        sys::mmcmc_rank_diagnostics(owned.as_ptr() as *const c_void, 0, sys::MMCMC_F32, c, n, p, rhat.as_mut_ptr(), rparts.as_mut_ptr(), bulk.as_mut_ptr(), tail.as_mut_ptr(), tparts.as_mut_ptr(), std::ptr::null(), 0, null_mut(), 0, null_mut())
+    })?;
+    Ok(RankDiagnostics { rhat, rhat_parts: rparts, ess_bulk: bulk, ess_tail: tail, ess_tail_parts: tparts })
+}
+
 /// `RunStats` (stats.rs:338-342): summaries of ESS and split R-hat over the parameters.
 pub type RunStats = sys::mmcmc_run_stats;
 
