@@ -399,6 +399,14 @@ int eh_lnu_f32(const float *u, size_t n, float *out)
     return 0;
 }
 
+/* the product's f64 logarithm (mm_math.h: mm_log), which turns the f64 accept uniform into ln u, value by value */
+int eh_log_f64(const double *u, size_t n, double *out)
+{
+    for (size_t i = 0; i < n; ++i)
+        out[i] = mm_log(u[i]);
+    return 0;
+}
+
 /* the NUTS leaf's acceptance statistic as the product evaluates it (mm_nuts.h: mm_accept_stat, a branch that skips the
  * exponential for d >= 0) beside the form it replaced, min(1, exp(d)): out_new, out_old [n] (tests/test_step_parity.py) */
 int eh_accept_stat(int dtype, const void *d, size_t n, void *out_new, void *out_old)

@@ -761,6 +761,17 @@ def engine_host_lnu_f32(u):
     return out
 
 
+def engine_host_log_f64(u):
+    """The PRODUCT's f64 logarithm (mm_math.h: mm_log) compiled for the host: ln u of the f64 accept uniform."""
+    x = np.ascontiguousarray(u, dtype=np.float64)
+    out = np.empty(x.shape, dtype=np.float64)
+    E = engine_host_lib()
+    E.eh_log_f64.restype = C.c_int
+    E.eh_log_f64.argtypes = [_dp, C.c_size_t, _dp]
+    E.eh_log_f64(_d(x), x.size, _d(out))
+    return out
+
+
 def engine_host_icdf24(words):
     """The PRODUCT's f32 normal (mm_rng.h: mm_icdf_f32) compiled for the host, one per Philox word."""
     w = np.ascontiguousarray(words, dtype=np.uint32)

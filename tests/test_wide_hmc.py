@@ -50,7 +50,7 @@ def test_wide_hmc_f64_vs_reference_order_and_runtime_d_kernel(M, O, dim):
         g = M.hmc.HMC(tgt, init, eps, 12).set_seed(3).set_kernel_variant(6)
         out6 = g.run(8, 3)
         assert np.array_equal(acc, g.accept_counts), name
-        np.testing.assert_allclose(out, out6, rtol=1e-10, atol=1e-10, err_msg=name)
+        assert np.array_equal(out, out6), name  # equal decisions: the same bits (tests/test_wide_hmc_edges.py)
         # a continued handle and a chain offset: the stream is keyed by (chain, iteration)
         c = M.hmc.HMC(tgt, init, eps, 12).set_seed(3)
         parts = np.concatenate([c.run(4, 3), c.run(4, 0)], axis=1)
@@ -79,7 +79,6 @@ def test_wide_hmc_f32_reference_benchmark_shape(M, O):
     r = o.run(2, 0, n_threads=2)
     assert np.array_equal(s2.accept_counts, o.accept_counts)
     np.testing.assert_allclose(g[:, 0], r[:, 0], rtol=2e-3, atol=2e-3)
-    assert np.array_equal(g, out[:, :0].reshape(6, 0, dim)) or True  # (run(100, 100) discards these rows)
 
 
 def test_wide_hmc_posterior_of_a_high_dimensional_gaussian(M, O):

@@ -7,9 +7,14 @@
   - lane-group NUTS (D = 16, 32, f64): the persistent scheduler against the single launch;
   - MH / HMC at the compiled dimensions up to 8: the four-waves-per-SIMD kernel (5) against the one-wave kernels (0, 2), any
     chain count, run length, iterations per launch, f32 and f64;
+  - w: HMC with one chain per workgroup (variant 8, csrc/mm_wide.hip) against the run-time-dimension kernel (6): random D in
+    [4, 32768] biased to the switches of the coordinates per thread (4096 | 4097, 8192 | 8193, 16384 | 16385) and to multiples
+    of 64 K, 1 - 8 chains, 0 - 6 leapfrog steps, f32 and f64; equal accept counts => equal bits; the two kernels order the
+    three sums of a transition differently, so a differing accept count is reported with its float64 margin m and is a
+    failure only when |m| > tau (m, tau: tests/test_wide_hmc_edges.py);
   - diagnostics: the power-spectrum kernel against the direct sums (R-hat / ESS to 1e-4 / 2e-3); x: long half-chains
     (N1 residues, any N1) against the direct sums.
-usage: python tools/fuzz_variants.py [seconds per family, default 40] [families: any of d g t n l h s x m, default dgtnlhsxm]"""
+usage: python tools/fuzz_variants.py [seconds per family, default 40] [families: any of d g t n l h w s x m, default dgtnlhwsxm]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -20,7 +25,7 @@ from mini_mcmc_amd.distributions import IsotropicGaussian, RosenbrockND, Standar
 from mini_mcmc_amd.nuts import NUTS
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 40.0
-fam = sys.argv[2] if len(sys.argv) > 2 else "dgtnlhsxm"
+fam = sys.argv[2] if len(sys.argv) > 2 else "dgtnlhwsxm"
 rng = np.random.default_rng(int(time.time()) & 0xffff)
 print("seed", rng.bit_generator.state["state"]["state"] & 0xffff)
 
@@ -168,6 +173,59 @@ while "h" in fam and time.time() - t0 < budget:
         assert all(np.array_equal(x, y) for x, y in zip(o, outs[0])), (type(tgt).__name__, tgt.dim, dt.__name__, C, nc, nd, ipl, seed, hmc)
     n += 1
 print(f"MH / HMC: {n} random cases, default kernel == one-wave kernels")
+
+t0, n, n_margin = time.time(), 0, 0
+if "w" in fam:
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import oracle as O  # the checker: the engine's noise on the host, for the float64 margin of a differing decision
+    import test_wide_hmc_edges as W
+while "w" in fam and time.time() - t0 < budget:
+    r = rng.random()
+    if r < 0.35:
+        d = int(rng.choice([4096, 8192, 16384, 32768])) + int(rng.integers(-2, 2)) * int(rng.random() < 0.7)
+    elif r < 0.6:
+        k = int(rng.choice([4, 8, 16, 32]))
+        d = 64 * k * int(rng.integers(1 if k == 4 else 9, 17)) + int(rng.integers(-1, 2))
+    else:
+        d = int(rng.integers(4, 32769))
+    d = min(max(d, 4), 32768)
+    dt = np.float32 if rng.random() < 0.5 else np.float64
+    kind = [W.ROS, W.ISO, W.STD][int(rng.integers(3))]
+    tgt = {W.ROS: RosenbrockND(d), W.ISO: IsotropicGaussian(W.SIGMA, d), W.STD: StandardNormal(d)}[kind]
+    C, nl, nc = int(rng.integers(1, 9)), int(rng.integers(0, 7)), int(rng.integers(1, 5))
+    eps = float(rng.uniform(0.5, 1.5)) * (0.02 if kind == W.ROS else (W.SIGMA if kind == W.ISO else 1.0)) * d ** -0.25
+    init = (init_with_seed(C, d, int(rng.integers(1000))) * (0.3 if kind == W.ROS else 1.0)).astype(dt)
+    seed = int(rng.integers(1 << 30))
+    res = []
+    for v in (8, 6):
+        s_ = HMC(tgt, init, eps, nl).set_seed(seed)
+        try:
+            s_.set_kernel_variant(v)
+        except Exception:
+            assert v == 8 and 8 < d <= 32, (v, d)  # served by a run-time compiled unit: no workgroup-per-chain form there
+            break
+        res.append((s_.run(nc, 0), s_.state(), s_.accept_counts.copy()))
+    if len(res) < 2:
+        continue
+    (o8, s8, a8), (o6, s6, a6) = res
+    what = (kind, d, dt.__name__, C, nl, nc, eps, seed)
+    if np.array_equal(a8, a6):
+        assert np.array_equal(o8, o6, equal_nan=True) and np.array_equal(s8, s6, equal_nan=True), what
+    else:
+        # the first transition at which a chain's rows part: its margin in float64, from the row both kernels still share
+        c, t = (int(v) for v in np.argwhere((o8 != o6).any(axis=2))[0])
+        prev = o6[:, t - 1] if t else init
+        z, u = O.engine_host_noise(seed, 0, t, C, d, dt)
+        dh = W._transition(kind, prev, z, float(dt(eps)), nl)[1]
+        dh_seq = W._transition(kind, prev, z, float(dt(eps)), nl, dtype=dt, seq=True)[1]
+        err = np.abs(dh_seq - dh)
+        m, tau = float(dh[c] - W._ln_u(O, u, dt)[c]), 4.0 * float(err[np.isfinite(err)].max(initial=0.0))  # tau over the case's chains
+        print(f"  variant 8 / 6 decide differently at chain {c}, transition {t}: m = {m:.3g}, tau = {tau:.3g}", what)
+        assert abs(m) <= tau, ("a differing accept decision outside the rounding of the sums", what, m, tau)
+        n_margin += 1
+    n += 1
+if "w" in fam:
+    print(f"wide HMC: {n} random cases, one chain per workgroup == run-time-dimension kernel ({n_margin} decided within rounding)")
 
 t0, n = time.time(), 0
 while "s" in fam and time.time() - t0 < budget:
