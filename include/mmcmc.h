@@ -310,6 +310,35 @@ int mmcmc_hmc_kernel_variant(mmcmc_hmc *h); /* the variant in use (>= 0) or a ne
 #define MMCMC_USER_KIND_BASE 1000
 int mmcmc_target_register_source(const char *name, int dim, const char *hip_source, int *kind_out, char *log, size_t log_len);
 
+/* The same from the log-density ALONE: the GPU analogue of the default body of `GradientTarget::unnorm_logp_and_grad`, which
+ * differentiates `unnorm_logp` through burn's autodiff (distributions.rs:78-88).  `hip_source` defines
+ *     template <class T> struct mmcmc_user_logp {
+ *         static constexpr int dim = <dim>;
+ *         template <class S> MM_HD static S logp(const mm_tparams<T> &P, const S *x);   // written ONCE over the scalar type S
+ *     };
+ * and the library appends the adapter mmcmc_user_target<T>: logp is logp<T>, logp_grad is forward-mode automatic
+ * differentiation of the same body with S = mm_dual<T, W> (csrc/mm_autodiff.h: a value and W tangents, in registers).  The
+ * functor then goes exactly the way of mmcmc_target_register_source -- the same kernels, the same checks, the same status
+ * codes (MMCMC_ERR_NO_DEVICE without a GPU) -- and the kind is accepted wherever a user kind is: MH, HMC, NUTS, the device
+ * groups, mmcmc_logp_grad_batch, and as the target of mmcmc_proposal_register_source.
+ *   Differentiable: + - * / and unary minus in every S / T combination, mm_fma, mm_logT, mm_expT, mm_sqrtT, mm_absT,
+ *   mm_maxT, mm_minT; S(c) makes a constant; < > <= >= compare values, so a body may branch on them.  Anything else called
+ *   on an S (mm_logf, sinf, ...) has no dual overload: the unit does not compile and the compiler's text arrives in `log`.
+ *   Constants and parameters written as T (T(100) * t, P.p[0] * x[0]) cost one multiplication per tangent, the same written
+ *   as S (S(100) * t) two operations: prefer T where the body allows it.
+ *   Cost: ceil(dim / W) passes, W = min(dim, 8), each about (1 + W) x logp -- against about 2 x logp for a hand-written
+ *   gradient.  A density whose gradient is needed at speed keeps mmcmc_target_register_source.
+ *   Loops over the coordinates must be fully unrolled -- write MM_UNROLL in front of them.  A loop left rolled indexes the
+ *   array of dual numbers at run time, and the compiler then keeps that array in private (scratch) memory instead of
+ *   registers: the RosenbrockND body at dim 32 without the pragma costs 1168 B (f32) / 2592 B (f64) per lane.
+ *   Singular points: the tangent of mm_sqrtT(a) divides by sqrt(a) and that of mm_logT(a) by a, so both are inf / NaN at
+ *   a = 0, as the derivatives themselves are.
+ *   Kinks: mm_absT at 0 and mm_maxT / mm_minT at a tie take ONE side's derivative (d|x| = +dx at 0; a tie takes the second
+ *   argument's tangents); a branch differentiates the side it takes.
+ *   The value returned next to the gradient equals logp<T> bit for bit, and host and device agree bit for bit
+ *   (-ffp-contract=off; every derivative formula has one fixed operation order). */
+int mmcmc_target_register_logp_source(const char *name, int dim, const char *hip_source, int *kind_out, char *log, size_t log_len);
+
 /* Which compiler builds run-time compiled units (process-wide; default AUTO).  AUTO: `hipcc --genco` in a child process
  * wherever hipcc is found (PATH, then /opt/rocm/bin), hipRTC (libhiprtc.so, bound at run time) otherwise.  A hipRTC was
  * caught miscompiling one kernel of these units that hipcc compiles correctly, hence the order; it was the copy PyTorch

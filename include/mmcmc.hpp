@@ -466,19 +466,36 @@ template <class T> class HMC {
 /* ---- a target of the user's own: the GPU analogue of `impl GradientTarget for MyDensity` (distributions.rs:65-108).
  * `hip_source` defines `template <class T> struct mmcmc_user_target` (dim, logp, logp_grad; include/mmcmc.h); it is
  * compiled at run time and the returned Target is accepted wherever a built-in one is (MH / HMC, dim <= 32). ---- */
-inline Target UserTarget(const std::string &name, int dim, const std::string &hip_source, const std::vector<double> &params = {})
+namespace detail {
+typedef int (*register_source_fn)(const char *, int, const char *, int *, char *, size_t);
+inline Target register_target(register_source_fn fn, const char *what, const std::string &name, int dim, const std::string &source,
+                              const std::vector<double> &params)
 {
     int kind = 0;
     std::string log(1 << 16, '\0');
-    const int st = mmcmc_target_register_source(name.c_str(), dim, hip_source.c_str(), &kind, &log[0], log.size());
+    const int st = fn(name.c_str(), dim, source.c_str(), &kind, &log[0], log.size());
     if (st != MMCMC_OK)
-        throw Error(st, "mmcmc_target_register_source: " + std::string(log.c_str()));
+        throw Error(st, std::string(what) + ": " + std::string(log.c_str()));
     Target t;
     t.d.kind = kind;
     t.d.dim = dim;
     for (size_t i = 0; i < params.size() && i < 8; ++i)
         t.d.params[i] = params[i];
     return t;
+}
+} // namespace detail
+
+inline Target UserTarget(const std::string &name, int dim, const std::string &hip_source, const std::vector<double> &params = {})
+{
+    return detail::register_target(mmcmc_target_register_source, "mmcmc_target_register_source", name, dim, hip_source, params);
+}
+
+/* ... and from its log-density alone: `logp_source` defines `template <class T> struct mmcmc_user_logp` with
+ * `template <class S> S logp(P, const S *x)` (loops over the coordinates under MM_UNROLL); the gradient is forward-mode
+ * automatic differentiation of that body on the device (mmcmc_target_register_logp_source, include/mmcmc.h). */
+inline Target AutodiffTarget(const std::string &name, int dim, const std::string &logp_source, const std::vector<double> &params = {})
+{
+    return detail::register_target(mmcmc_target_register_logp_source, "mmcmc_target_register_logp_source", name, dim, logp_source, params);
 }
 
 /* ---- HMC over several GPUs from one call: run() executes every chain (ChainRunner::run, core.rs:176-186) ---- */

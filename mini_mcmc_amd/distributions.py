@@ -155,18 +155,40 @@ class UserTarget(Target):
     (`hipcc --genco` in a child process where hipcc is installed, else hipRTC) into the engine's MH / HMC kernels for f32 and f64 and its NUTS kernel for the three type modes.  `params` (up to 8 numbers) arrive as `P.p[i]`,
     `matrix` ([dim, dim]) as `P.mat`.  `UserTarget.compile_log` holds the compiler's diagnostics."""
 
+    _register = "mmcmc_target_register_source"
+
     def __init__(self, name: str, dim: int, source: str, params=(), matrix=None):
         super().__init__(dim, params, matrix)
         kind = C.c_int(0)
         log = C.create_string_buffer(1 << 16)
-        st = L.lib().mmcmc_target_register_source(name.encode(), int(dim), source.encode(), C.byref(kind), log, len(log))
+        st = getattr(L.lib(), self._register)(name.encode(), int(dim), source.encode(), C.byref(kind), log, len(log))
         self.compile_log = log.value.decode(errors="replace")
         if st != L.OK:
-            raise L.MmcmcError(st, "mmcmc_target_register_source" + (": " + self.compile_log[-2000:] if self.compile_log else ""))
+            raise L.MmcmcError(st, self._register + (": " + self.compile_log[-2000:] if self.compile_log else ""))
         self.kind = kind.value
         self.name = name
         #: "hipcc" (`hipcc --genco` in a child process: the default wherever hipcc is installed) or "hiprtc"
         self.compiler = {1: "hipcc", 2: "hiprtc"}.get(L.lib().mmcmc_rtc_unit_compiler(self.kind), "?")
+
+
+class AutodiffTarget(UserTarget):
+    """A target from its log-density alone: the GPU analogue of the default `GradientTarget::unnorm_logp_and_grad`, which
+    differentiates `unnorm_logp` (distributions.rs:78-88).
+
+    `logp_source` is HIP C++ defining `template <class T> struct mmcmc_user_logp` with `static constexpr int dim` and
+    `template <class S> MM_HD static S logp(const mm_tparams<T> &P, const S *x)`, written once over the scalar type `S`
+    (include/mmcmc.h: mmcmc_target_register_logp_source lists the differentiable operations).  The gradient HMC and NUTS
+    need is forward-mode automatic differentiation of that body on the device (csrc/mm_autodiff.h); everything else is
+    `UserTarget`'s.
+
+    Put `MM_UNROLL` in front of every loop over the coordinates: a loop left rolled indexes the array of dual numbers at run
+    time, which moves it from registers to scratch memory (at dim 32: 1168 B per lane in f32, 2592 B in f64).  The tangents
+    of `mm_sqrtT(a)` and `mm_logT(a)` divide by sqrt(a) and a: inf / NaN at a = 0, like the derivatives themselves."""
+
+    _register = "mmcmc_target_register_logp_source"
+
+    def __init__(self, name: str, dim: int, logp_source: str, params=(), matrix=None):
+        super().__init__(name, dim, logp_source, params, matrix)
 
 
 RTC_COMPILERS = {"auto": 0, "hipcc": 1, "hiprtc": 2}

@@ -612,10 +612,18 @@ impl<T: GpuFloat> Drop for GpuMhGroup<T> {
 /// GPU analogue of implementing `Target` / `GradientTarget` / `Proposal` (distributions.rs:65-108) oneself.  Returns the
 /// kind to put into a target / proposal description, or the compiler's log.
 pub fn register_target_source(name: &str, dim: usize, hip_source: &str) -> Result<i32, String> {
-    let (n, s) = (std::ffi::CString::new(name).unwrap(), std::ffi::CString::new(hip_source).unwrap());
+    register_target_with(sys::mmcmc_target_register_source, name, dim, hip_source)
+}
+/// The same from the log-density alone (`mmcmc_target_register_logp_source`): the gradient is forward-mode autodiff on the device.
+pub fn register_target_logp_source(name: &str, dim: usize, logp_source: &str) -> Result<i32, String> {
+    register_target_with(sys::mmcmc_target_register_logp_source, name, dim, logp_source)
+}
+type RegisterTargetFn = unsafe extern "C" fn(*const std::os::raw::c_char, c_int, *const std::os::raw::c_char, *mut c_int, *mut std::os::raw::c_char, usize) -> c_int;
+fn register_target_with(register: RegisterTargetFn, name: &str, dim: usize, source: &str) -> Result<i32, String> {
+    let (n, s) = (std::ffi::CString::new(name).unwrap(), std::ffi::CString::new(source).unwrap());
     let mut kind: c_int = 0;
     let mut log = vec![0 as std::os::raw::c_char; 1 << 16];
-    let st = unsafe { sys::mmcmc_target_register_source(n.as_ptr(), dim as c_int, s.as_ptr(), &mut kind, log.as_mut_ptr(), log.len()) };
+    let st = unsafe { register(n.as_ptr(), dim as c_int, s.as_ptr(), &mut kind, log.as_mut_ptr(), log.len()) };
     if st == sys::MMCMC_OK { Ok(kind) } else { Err(unsafe { CStr::from_ptr(log.as_ptr()) }.to_string_lossy().into_owned()) }
 }
 pub fn register_proposal_source(name: &str, target_kind: i32, dim: usize, hip_source: &str) -> Result<i32, String> {

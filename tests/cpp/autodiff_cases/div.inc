@@ -1,0 +1,7 @@
+/* division: -x0 / (1 + x1^2) */
+template <class T> struct mmcmc_user_logp {
+    static constexpr int dim = 2;
+    template <class S> MM_HD static S logp(const mm_tparams<T> &, const S *x) {
+        return -(x[0] / (S(1) + x[1] * x[1]));
+    }
+};
