@@ -9,7 +9,8 @@
  *                     mean    = (mean * (n-1) + x) / n
  *                     mean_sq = n == 1 ? x^2 : (mean_sq * (n-1) + x^2) / n
  *                 -- per chain these are exactly the reference's values -- and a flag "this state differs from the
- *                 chain's previous one" per (step, chain).
+ *                 chain's previous one" per (step, chain).  Every chain's state and every flag byte of each kernel and
+ *                 path below is compared bit for bit with a numpy restatement in tests/test_tracker_edges.py.
  *   p_accept      the reference folds p <- (1-a) p + a * flag over the chains of a step IN ORDER, step after step
  *                 (a = 0.01, stats.rs:252-258): one long recurrence.  Its value forgets its start at the rate
  *                 0.99^m, so one lane replays the last 16 384 flags sequentially (0.99^16384 ~ 1e-72): the same f32
