@@ -143,38 +143,6 @@ struct mm_nuts_lg_args {
 #endif
 };
 
-/* build switches of the experiments kept for comparison */
-#ifndef MM_LG_ASM_MFMA
-#define MM_LG_ASM_MFMA 1
-#endif
-#ifndef MM_LG_AUX_SHARED
-#define MM_LG_AUX_SHARED 1
-#endif
-#ifndef MM_LG_PAIR_UNROLL
-#define MM_LG_PAIR_UNROLL 0 /* two pairs per trip (leaf index mod 4 constant): 468 -> 465 ms for 30 % more code: off */
-#endif
-#ifndef MM_LG_LEAN
-#define MM_LG_LEAN 1 /* round 5: the leaf loop without lane guards (mm_lg_doubling: "lean pair loop"); 0 = the guarded loop only */
-#endif
-#ifndef MM_LG_F_RECENT
-#define MM_LG_F_RECENT 1 /* round 6: the last LDS first-leaf slot keeps the most recent leaf with c >= LF + 1 (load_rec); 0 = slot per c only */
-#endif
-#ifndef MM_LG_CHECK_FORM
-#define MM_LG_CHECK_FORM 3 /* round 6 (profiles/r6i_, r6j_nuts_check_form*_probe.log; best case 2873 cycles per leaf iteration): 0 = the check and its rare case inside the pair loop (round 5); 1 = its branch marked unlikely (2879); 2 = the three conditions as 64-bit lane masks on the scalar unit (2833); 3 = 2 + the rare case handled OUTSIDE the fast loop, which is left and entered again (2789; without any check: 2725) */
-#endif
-#ifndef MM_LG_DEEP_EARLY
-#define MM_LG_DEEP_EARLY 0 /* round 6 experiment: the level-(WU + 1) merge's HBM records requested ahead of the LDS-level merges */
-#endif
-#ifndef MM_LG_TOUCH
-#define MM_LG_TOUCH 0 /* round 6 experiment: touch the HBM records of a pair's level-(LE + 1) merge two leaves ahead */
-#endif
-#ifndef MM_LG_PINGPONG
-#define MM_LG_PINGPONG 1 /* round 6: the pair's two leaves write (x, p) alternately into the first-leaf copy and back (no register copies); 0 = in place + copy */
-#endif
-#ifndef MM_LG_WALK_UNROLL
-#define MM_LG_WALK_UNROLL 3 /* config 5: 0 510 ms, 1 496, 2 473, 3 469, 4 470 */
-#endif
-
 /* OCC = waves per SIMD the kernel is built for: 1 = the 512-register budget and 40 KB of LDS per wave; 2 = 256 registers
  * and 20 KB (persistent scheduler only).  Level 0 of the pending-subtree stack never reaches memory: leaves are taken
  * in pairs and the first leaf's subtree waits for its sibling in registers (so does its (x, p) for the stop criterion).
@@ -188,6 +156,9 @@ template <int D, int OCC = 1> struct mm_lg_cfg {
     static constexpr int FS = 2 * NS;          /* first-leaf record: x[NS], p[NS] */
     static constexpr int LE = OCC == 1 ? 3 : 2; /* entry(k), 1 <= k <= LE, in LDS */
     static constexpr int LF = OCC == 1 ? 3 : 1; /* first(c), 2 <= c <= 1 + LF, in LDS */
+    /* walk levels 1 .. WU of a pair are straight-line code (walk_up, the lean pair loop); the two-waves-per-SIMD build is
+     * slower with it (518 -> 582 ms) */
+    static constexpr int WU = OCC == 1 ? 3 : 0;
     static constexpr int lds_E = 0, lds_F = LE * ES, lds_slots = LE * ES + LF * FS;
     static constexpr size_t lds_bytes = (size_t)lds_slots * 64 * sizeof(double);
     /* HBM slots per wave: entry(k), k = LE + 1 .. JMAX - 1 | first(c), c = LF + 2 .. JMAX */
@@ -311,7 +282,6 @@ template <int D, bool ALDS = false, class Lane>
 __device__ __forceinline__ void mm_lg_ax(const Lane &L, const double *x, double *y)
 {
     constexpr int NS = D / 4, NT = D / 16;
-#if MM_LG_ASM_MFMA
     /* The A-operand blocks stay in accumulation registers and the MFMA reads them there ("a"), the products land in
      * ordinary registers ("v").  Through the builtin the compiler parks the blocks in AGPRs too, but copies each to a
      * VGPR before its MFMA (2 v_accvgpr_read + a wait state) and accumulates in AGPRs that it reads back (16 more):
@@ -368,7 +338,6 @@ __device__ __forceinline__ void mm_lg_ax(const Lane &L, const double *x, double 
             y[r] = acc0[r];
         return;
     }
-#endif
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         mm_d4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -466,14 +435,6 @@ template <int D> __device__ __forceinline__ double mm_lg_aux_peek(mm_lg_lane<D> 
      * 4 g + q) instead of four copies of one, so the ten Philox rounds run once per eight draws, not once per two;
      * the draw is fetched from the lane that holds its block through the LDS crossbar (ds_bpermute: no memory).  The
      * lanes of a chain share aux_k, so they refill in the same call. */
-#if !MM_LG_AUX_SHARED
-    const unsigned int b1 = L.aux_k >> 1;
-    if (b1 != L.aux_have) {
-        L.aux_blk = mm_block(seed, L.chain, L.m, MM_AUX_BLOCK + b1);
-        L.aux_have = b1;
-    }
-    return (L.aux_k & 1u) ? mm_u53(L.aux_blk.w[2], L.aux_blk.w[3]) : mm_u53(L.aux_blk.w[0], L.aux_blk.w[1]);
-#endif
     const unsigned int b = L.aux_k >> 1, g = b >> 2;
     if (g != L.aux_have) {
         L.aux_blk = mm_block(seed, L.chain, L.m, MM_AUX_BLOCK + 4u * g + (unsigned int)L.q);
@@ -604,9 +565,6 @@ template <int D, bool COH = false, int OCC = 1> __device__ __forceinline__ void 
 
 /* doubling j of the wave's chains (one iteration of `while s`, nuts.rs:578-671); `alive` in: the chain takes part,
  * out: it wants another doubling */
-#ifndef MM_LG_UNIFORM_J
-#define MM_LG_UNIFORM_J 1 /* round 6: the doubling's level as an SGPR (below); 0 = as the caller hands it over */
-#endif
 template <int D, bool COH, int OCC, bool RES>
 __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_lg_args &a, int j_in, bool &alive,
                                                double epsilon, mm_lds_double *lds, double *scr, mm_lg_edges<D> &E)
@@ -617,11 +575,7 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
      * the pair loop was compiled as a DIVERGENT loop (exit mask accumulated in SGPR pairs, s_and_saveexec around every walk
      * level, phi copies of the edge at the back edge, a full s_waitcnt at the join).  One v_readfirstlane makes all of it
      * scalar control flow. */
-#if MM_LG_UNIFORM_J
     const int j = __builtin_amdgcn_readfirstlane(j_in);
-#else
-    const int j = j_in;
-#endif
     using Cfg = mm_lg_cfg<D, OCC>;
     constexpr int NS = Cfg::NS, ES = Cfg::ES;
     const size_t st = (size_t)a.c_pad * 4;
@@ -631,10 +585,6 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
         double fx[NS], fp[NS], prime[NS], alpha, cnt;
     };
     auto load_rec = [&](int k, int cc, rec &r) __attribute__((always_inline)) {
-#ifdef MM_LG_EXPERIMENT_NO_HBM /* timing experiment only (wrong trees): every record in LDS */
-        cc = cc > 1 + Cfg::LF + MM_LG_EXPERIMENT_NO_HBM ? 1 + Cfg::LF + MM_LG_EXPERIMENT_NO_HBM : cc;
-        k = k > Cfg::LE + MM_LG_EXPERIMENT_NO_HBM ? Cfg::LE + MM_LG_EXPERIMENT_NO_HBM : k;
-#endif
         /* Three cases, each ONE block that issues all 26 loads before anything waits: written as two independent
          * if / else (first-leaf record, then entry) the entry's loads were sunk below the stop criterion, i.e. behind
          * the first-leaf record's wait -- two memory latencies per merge where the records are in HBM.  An entry
@@ -662,7 +612,7 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
         if (k > Cfg::LE)
             take((const double *)(scr + (size_t)(Cfg::hbm_F + (cc - 2 - Cfg::LF) * Cfg::FS) * 64),
                  (const double *)(scr + (size_t)(Cfg::hbm_E + (k - 1 - Cfg::LE) * ES) * 64));
-        else if (MM_LG_F_RECENT ? k > Cfg::LF : cc > 1 + Cfg::LF)
+        else if (k > Cfg::LF)
             take((const double *)(scr + (size_t)(Cfg::hbm_F + (cc - 2 - Cfg::LF) * Cfg::FS) * 64),
                  (const mm_lds_double *)(lds + (size_t)(Cfg::lds_E + (k - 1) * ES) * 64));
         else
@@ -767,23 +717,19 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
              * leaf of a level-1 subtree waits in registers, below) */
             if (j > 1 && (leaf & 3u) == 0u) {
                 int cc = leaf ? (__ffs((int)leaf) - 1) : MM_NUTS_JMAX;
-#ifdef MM_LG_EXPERIMENT_NO_HBM
-                cc = cc > 1 + Cfg::LF + MM_LG_EXPERIMENT_NO_HBM ? 1 + Cfg::LF + MM_LG_EXPERIMENT_NO_HBM : cc;
-#endif
-                if (MM_LG_F_RECENT || cc <= 1 + Cfg::LF) { /* always in LDS: under c, or in the last slot ("the most recent leaf with c >= LF + 1", load_rec) */
-                    mm_lds_double *f = lds + (size_t)(Cfg::lds_F + ((cc > Cfg::LF + 1 ? Cfg::LF + 1 : cc) - 2) * Cfg::FS) * 64;
+                /* always in LDS: under c, or in the last slot ("the most recent leaf with c >= LF + 1", load_rec) */
+                mm_lds_double *f = lds + (size_t)(Cfg::lds_F + ((cc > Cfg::LF + 1 ? Cfg::LF + 1 : cc) - 2) * Cfg::FS) * 64;
 #pragma unroll
-                    for (int s = 0; s < NS; ++s) {
-                        f[s * 64] = cx[s];
-                        f[(NS + s) * 64] = cp[s];
-                    }
+                for (int s = 0; s < NS; ++s) {
+                    f[s * 64] = cx[s];
+                    f[(NS + s) * 64] = cp[s];
                 }
                 if (cc > 1 + Cfg::LF) { /* and under c in HBM for the merges at levels > LF */
-                    double *f = scr + (size_t)(Cfg::hbm_F + (cc - 2 - Cfg::LF) * Cfg::FS) * 64;
+                    double *fh = scr + (size_t)(Cfg::hbm_F + (cc - 2 - Cfg::LF) * Cfg::FS) * 64;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
-                        f[s * 64] = cx[s];
-                        f[(NS + s) * 64] = cp[s];
+                        fh[s * 64] = cx[s];
+                        fh[(NS + s) * 64] = cp[s];
                     }
                 }
             }
@@ -840,9 +786,6 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
     /* first child at level k >= 1: wait for the sibling if still valid; with s' = 0 the parent returns it as it is, so
      * it keeps walking */
     auto push = [&](int k) __attribute__((always_inline)) {
-#ifdef MM_LG_EXPERIMENT_NO_HBM
-        k = k > Cfg::LE + MM_LG_EXPERIMENT_NO_HBM ? Cfg::LE + MM_LG_EXPERIMENT_NO_HBM : k;
-#endif
         MM_LG_TICK(L, 3);
         MM_LG_COUNT(L, 13);
         if (walking && S_s) {
@@ -879,9 +822,9 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
         }
     };
     auto walk_up = [&](unsigned int leaf) __attribute__((always_inline)) {
-        /* levels 1 .. MM_LG_WALK_UNROLL (7 of 8 merges at 2 levels) are straight-line code with the level a constant:
+        /* levels 1 .. Cfg::WU (7 of 8 merges at 2 levels) are straight-line code with the level a constant:
          * fixed LDS addresses, no loop-carried copies of the subtree's scalars */
-        constexpr int WU = OCC == 2 ? 0 : MM_LG_WALK_UNROLL; /* the two-waves-per-SIMD build is slower with it (518 -> 582 ms) */
+        constexpr int WU = Cfg::WU;
         bool more = true;
 #pragma unroll
         for (int k = 1; k <= WU; ++k) {
@@ -953,7 +896,7 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
      * test_nuts_config5_full_size_*). */
     bool lean = false;
     unsigned int ka = 0;
-    if constexpr (MM_LG_LEAN && OCC == 1) {
+    if constexpr (OCC == 1) {
         const unsigned long long am = __ballot(alive);
         if (j >= 1 && am != 0ull) {
             ka = (unsigned int)__builtin_amdgcn_readlane((int)L.aux_k, (int)__ffsll((long long)am) - 1);
@@ -968,15 +911,7 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
         unsigned int have_s = 0xffffffffu; /* the first draw refills */
         const int lane15x4 = (L.lane & 15) * 4;
         auto draw = [&]() __attribute__((always_inline)) -> double {
-#ifdef MM_LG_EXP_CHEAP_DRAW
-            ka += 1u;
-            return 0.25 + 1e-9 * (double)ka;
-#endif
-#if MM_LG_UNIFORM_J
             const unsigned int kau = (unsigned int)__builtin_amdgcn_readfirstlane((int)ka); /* lock-step draws: one index for the wave */
-#else
-            const unsigned int kau = ka;
-#endif
             const unsigned int b = kau >> 1, g = b >> 2;
             if (g != have_s) {
                 L.aux_blk = mm_block(a.seed, L.chain, L.m, MM_AUX_BLOCK + 4u * g + (unsigned int)L.q);
@@ -990,30 +925,21 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
             return mm_u53(hi, lo);
         };
         /* (xi, pi) -> (xo, po): the pair's first leaf reads the edge and writes the first-leaf copy, the second reads that
-         * and writes the edge (MM_LG_PINGPONG); in place when xo == xi */
+         * and writes the edge: no register copies */
         auto leaf_io = [&](unsigned int leaf, const double *xi, const double *pi, double *xo, double *po) __attribute__((always_inline)) {
             MM_LG_COUNT(L, 6);
             leaf_iters += 1u;
             double ph[NS];
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-#if MM_LG_PINGPONG
                 ph[s] = mm_fma3(nh, cg[s], pi[s]);
                 xo[s] = mm_fma3(epsv, ph[s], xi[s]);
-#else
-                ph[s] = fma(nh, cg[s], pi[s]);
-                xo[s] = fma(epsv, ph[s], xi[s]);
-#endif
             }
             mm_lg_ax<D, false>(L, xo, cg);
             double xy = 0.0, pp = 0.0;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-#if MM_LG_PINGPONG
                 po[s] = mm_fma3(nh, cg[s], ph[s]);
-#else
-                po[s] = fma(nh, cg[s], ph[s]);
-#endif
                 xy = fma(xo[s], cg[s], xy);
                 pp = fma(po[s], po[s], pp);
             }
@@ -1024,26 +950,21 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
             S_n = (L.logu < jointp) ? 1u : 0u;
             S_s = (L.logu - 1000.0) < jointp;
             S_nalpha = 1;
-#ifdef MM_LG_EXP_NO_FILING /* timing experiments of tools/experiments/nuts_lg_lean_strip.sh: wrong trees */
-            if (false) {
-#else
             if (j > 1 && (leaf & 3u) == 0u) {
-#endif
                 const int cc = leaf ? (__ffs((int)leaf) - 1) : MM_NUTS_JMAX;
-                if (MM_LG_F_RECENT || cc <= 1 + Cfg::LF) { /* always in LDS: under c, or in the last slot ("the most recent leaf with c >= LF + 1", load_rec) */
-                    mm_lds_double *f = lds + (size_t)(Cfg::lds_F + ((cc > Cfg::LF + 1 ? Cfg::LF + 1 : cc) - 2) * Cfg::FS) * 64;
+                /* always in LDS: under c, or in the last slot ("the most recent leaf with c >= LF + 1", load_rec) */
+                mm_lds_double *f = lds + (size_t)(Cfg::lds_F + ((cc > Cfg::LF + 1 ? Cfg::LF + 1 : cc) - 2) * Cfg::FS) * 64;
 #pragma unroll
-                    for (int s = 0; s < NS; ++s) {
-                        f[s * 64] = xo[s];
-                        f[(NS + s) * 64] = po[s];
-                    }
+                for (int s = 0; s < NS; ++s) {
+                    f[s * 64] = xo[s];
+                    f[(NS + s) * 64] = po[s];
                 }
                 if (cc > 1 + Cfg::LF) { /* and under c in HBM for the merges at levels > LF */
-                    double *f = scr + (size_t)(Cfg::hbm_F + (cc - 2 - Cfg::LF) * Cfg::FS) * 64;
+                    double *fh = scr + (size_t)(Cfg::hbm_F + (cc - 2 - Cfg::LF) * Cfg::FS) * 64;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
-                        f[s * 64] = xo[s];
-                        f[(NS + s) * 64] = po[s];
+                        fh[s * 64] = xo[s];
+                        fh[(NS + s) * 64] = po[s];
                     }
                 }
             }
@@ -1111,13 +1032,12 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
                 live01 = 0u;
             }
         };
-        constexpr int WU = MM_LG_WALK_UNROLL;
-        /* what the pair hands to the validity check (and, MM_LG_CHECK_FORM 3, out of the fast loop) */
+        constexpr int WU = Cfg::WU;
+        /* what the pair hands to the validity check (and out of the fast loop) */
         unsigned int P_n = 0, P_nalpha = 0, lf1 = 0;
         double P_alpha = 0.0;
         bool first_ok = true;
         int k_stop = 0;
-#if MM_LG_CHECK_FORM == 3
         /* Round 6: the validity check LEAVES the pair loop instead of handling its case inside it.  The fast loop then changes
          * none of dead / live01 / died / F_* (they are invariant in it), carries no join behind a rare block, and its only
          * vector-dependent branch is one scalar test of three lane masks; the slow path (a chain retires: at most once per chain
@@ -1129,150 +1049,71 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
             unsigned long long m_inv1 = 0ull, m_inv2 = 0ull;
             bool slow = false;
             for (; leaf < n_leaves; leaf += 2) {
-#else
-        for (unsigned int leaf = 0; leaf < n_leaves; leaf += 2) {
-            if (__ballot(!dead) == 0ull)
-                break;
-#endif
-#if MM_LG_TOUCH
-            /* Round 6: a pair whose index ends in >= LE ones will merge at level LE + 1 with records that live in HBM (1/16 of
-             * the pairs at LE = 3; ~2000 cycles of exposed latency each: one wave per SIMD has nobody to hide it behind).  Their
-             * cache lines are TOUCHED here, two leaves ahead -- one 4-byte load per 128-byte line into a register nobody reads,
-             * two loads per lane -- so that the merge's own loads find them in the L1 / L2. */
-            if ((((leaf >> 1) + 1u) & ((1u << (Cfg::LE + 1)) - 1u)) == 0u && (int)Cfg::LE + 1 < j) {
-                const unsigned int lfp = leaf | 1u;
-                const unsigned int i0 = lfp & ~((2u << (Cfg::LE + 1)) - 1u);
-                const int cc = i0 ? (__ffs((int)i0) - 1) : MM_NUTS_JMAX;
-                const double *const scr0 = scr - L.lane; /* `scr` is the lane's own column of the wave's lane-interleaved slots */
-                const float *e = reinterpret_cast<const float *>(scr0 + (size_t)(Cfg::hbm_E + 0 * ES) * 64);
-                const float *f = reinterpret_cast<const float *>(scr0 + (size_t)(Cfg::hbm_F + (cc - 2 - Cfg::LF) * Cfg::FS) * 64);
-                float t0 = 0.f, t1 = 0.f;
-                if (L.lane * 32 < ES * 128)
-                    t0 = __builtin_nontemporal_load(e + L.lane * 32);
-                t1 = __builtin_nontemporal_load(f + L.lane * 32);
-                asm volatile("" ::"v"(t0), "v"(t1));
-            }
-#endif
-            /* ---- the first leaf of the pair: its one-leaf subtree waits for the sibling in registers */
-            double pfx[NS], pfp[NS];
-#if MM_LG_PINGPONG
-            leaf_io(leaf, cx, cp, pfx, pfp);
-#else
-            leaf_io(leaf, cx, cp, cx, cp);
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                pfx[s] = cx[s];
-                pfp[s] = cp[s];
-            }
-#endif
-            const double d_first = d_last;
-            P_n = S_n;
-            P_nalpha = S_nalpha;
-            /* a first leaf that is not valid is handed up as it is and its sibling never built (nuts.rs:858-899): here the lane
-             * runs on regardless and is set right at the end of the pair (ONE check per pair: a branch on a freshly computed
-             * lane mask drains the wave's pipeline) */
-            first_ok = S_s;
-            /* ---- its sibling, both acceptance statistics in one pass (even rows the first leaf's d, odd rows the second's),
-             *      the merge at level 0 */
-#if MM_LG_PINGPONG
-            leaf_io(leaf | 1u, pfx, pfp, cx, cp);
-#else
-            leaf_io(leaf | 1u, cx, cp, cx, cp);
-#endif
-            {
-                const double e = mm_lg_accept_prob((L.q & 1) ? d_last : d_first);
-                typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-                const unsigned int elo = (unsigned int)__double2loint(e), ehi = (unsigned int)__double2hiint(e);
-                const u2 l2 = __builtin_amdgcn_permlane16_swap(elo, elo, false, false);
-                const u2 h2 = __builtin_amdgcn_permlane16_swap(ehi, ehi, false, false);
-                P_alpha = __hiloint2double((int)h2[0], (int)l2[0]);
-                S_alpha = __hiloint2double((int)h2[1], (int)l2[1]);
-            }
-            merge_l(pfx, pfp, pfx, mm_true_t(), P_alpha, P_n, P_nalpha);
-            /* ---- the pair is handed up: merges at the levels of the trailing ones of the pair index, then a push */
-            lf1 = leaf | 1u;
-            k_stop = 0; /* the level of the push; j: the doubling is complete */
-            auto level = [&](int k) __attribute__((always_inline)) {
-                if (k >= j) {
-                    k_stop = j;
-                } else if ((lf1 >> k) & 1u) {
-                    rec rk;
-                    load_rec(k, first_slot(lf1, k), rk);
-                    const unsigned long long cnt = (unsigned long long)__double_as_longlong(rk.cnt);
-                    merge_l(rk.fx, rk.fp, rk.prime, mm_false_t(), rk.alpha, (unsigned int)cnt, (unsigned int)(cnt >> 32));
-                } else {
-                    const double cnt =
-                        __longlong_as_double((long long)((unsigned long long)S_n | ((unsigned long long)S_nalpha << 32)));
-                    if (k <= Cfg::LE) {
-                        mm_lds_double *e = lds + (size_t)(Cfg::lds_E + (k - 1) * ES) * 64;
-#pragma unroll
-                        for (int s = 0; s < NS; ++s)
-                            e[s * 64] = S_prime[s];
-                        e[NS * 64] = S_alpha;
-                        e[(NS + 1) * 64] = cnt;
+                /* ---- the first leaf of the pair: its one-leaf subtree waits for the sibling in registers */
+                double pfx[NS], pfp[NS];
+                leaf_io(leaf, cx, cp, pfx, pfp);
+                const double d_first = d_last;
+                P_n = S_n;
+                P_nalpha = S_nalpha;
+                /* a first leaf that is not valid is handed up as it is and its sibling never built (nuts.rs:858-899): here the lane
+                 * runs on regardless and is set right at the end of the pair (ONE check per pair: a branch on a freshly computed
+                 * lane mask drains the wave's pipeline) */
+                first_ok = S_s;
+                /* ---- its sibling, both acceptance statistics in one pass (even rows the first leaf's d, odd rows the second's),
+                 *      the merge at level 0 */
+                leaf_io(leaf | 1u, pfx, pfp, cx, cp);
+                {
+                    const double e = mm_lg_accept_prob((L.q & 1) ? d_last : d_first);
+                    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+                    const unsigned int elo = (unsigned int)__double2loint(e), ehi = (unsigned int)__double2hiint(e);
+                    const u2 l2 = __builtin_amdgcn_permlane16_swap(elo, elo, false, false);
+                    const u2 h2 = __builtin_amdgcn_permlane16_swap(ehi, ehi, false, false);
+                    P_alpha = __hiloint2double((int)h2[0], (int)l2[0]);
+                    S_alpha = __hiloint2double((int)h2[1], (int)l2[1]);
+                }
+                merge_l(pfx, pfp, pfx, mm_true_t(), P_alpha, P_n, P_nalpha);
+                /* ---- the pair is handed up: merges at the levels of the trailing ones of the pair index, then a push */
+                lf1 = leaf | 1u;
+                k_stop = 0; /* the level of the push; j: the doubling is complete */
+                auto level = [&](int k) __attribute__((always_inline)) {
+                    if (k >= j) {
+                        k_stop = j;
+                    } else if ((lf1 >> k) & 1u) {
+                        rec rk;
+                        load_rec(k, first_slot(lf1, k), rk);
+                        const unsigned long long cnt = (unsigned long long)__double_as_longlong(rk.cnt);
+                        merge_l(rk.fx, rk.fp, rk.prime, mm_false_t(), rk.alpha, (unsigned int)cnt, (unsigned int)(cnt >> 32));
                     } else {
-                        double *e = scr + (size_t)(Cfg::hbm_E + (k - 1 - Cfg::LE) * ES) * 64;
+                        const double cnt =
+                            __longlong_as_double((long long)((unsigned long long)S_n | ((unsigned long long)S_nalpha << 32)));
+                        if (k <= Cfg::LE) {
+                            mm_lds_double *e = lds + (size_t)(Cfg::lds_E + (k - 1) * ES) * 64;
 #pragma unroll
-                        for (int s = 0; s < NS; ++s)
-                            e[s * 64] = S_prime[s];
-                        e[NS * 64] = S_alpha;
-                        e[(NS + 1) * 64] = cnt;
+                            for (int s = 0; s < NS; ++s)
+                                e[s * 64] = S_prime[s];
+                            e[NS * 64] = S_alpha;
+                            e[(NS + 1) * 64] = cnt;
+                        } else {
+                            double *e = scr + (size_t)(Cfg::hbm_E + (k - 1 - Cfg::LE) * ES) * 64;
+#pragma unroll
+                            for (int s = 0; s < NS; ++s)
+                                e[s * 64] = S_prime[s];
+                            e[NS * 64] = S_alpha;
+                            e[(NS + 1) * 64] = cnt;
+                        }
+                        k_stop = k;
                     }
-                    k_stop = k;
-                }
-            };
-#ifdef MM_LG_EXP_FIXED_WALK
-            {
-                rec rk;
-                load_rec(1, 2, rk);
-                const unsigned long long cnt = (unsigned long long)__double_as_longlong(rk.cnt);
-                merge_l(rk.fx, rk.fp, rk.prime, mm_false_t(), rk.alpha, (unsigned int)cnt & 1u, (unsigned int)(cnt >> 32) & 1u);
-                mm_lds_double *e = lds + (size_t)(Cfg::lds_E) * 64;
+                };
 #pragma unroll
-                for (int s = 0; s < NS; ++s)
-                    e[s * 64] = S_prime[s];
-                e[NS * 64] = S_alpha;
-                e[(NS + 1) * 64] = __longlong_as_double((long long)((unsigned long long)S_n | ((unsigned long long)S_nalpha << 32)));
-                k_stop = (lf1 + 1u >= n_leaves) ? j : 1;
-            }
-#else
-#if MM_LG_DEEP_EARLY
-            /* Round 6 experiment: a pair whose index ends in WU + 1 ones merges at level WU + 1 with records from HBM.  Their
-             * loads depend on nothing the LDS-level merges compute, so they are issued BEFORE those (~1800 cycles of merges at
-             * levels 1 .. WU under the latency) instead of after them. */
-            constexpr int KD = WU + 1;
-            const bool deep = KD < j && (lf1 & ((2u << KD) - 1u)) == ((2u << KD) - 1u);
-            rec rdeep;
-            if (deep)
-                load_rec(KD, first_slot(lf1, KD), rdeep);
-#pragma unroll
-            for (int k = 1; k <= WU; ++k)
-                if (k_stop == 0)
+                for (int k = 1; k <= WU; ++k)
+                    if (k_stop == 0)
+                        level(k);
+                for (int k = WU + 1; k_stop == 0; ++k)
                     level(k);
-            if (k_stop == 0) {
-                if (deep) {
-                    const unsigned long long cnt = (unsigned long long)__double_as_longlong(rdeep.cnt);
-                    merge_l(rdeep.fx, rdeep.fp, rdeep.prime, mm_false_t(), rdeep.alpha, (unsigned int)cnt, (unsigned int)(cnt >> 32));
-                } else {
-                    level(KD);
-                }
-            }
-            for (int k = KD + 1; k_stop == 0; ++k)
-                level(k);
-#else
-#pragma unroll
-            for (int k = 1; k <= WU; ++k)
-                if (k_stop == 0)
-                    level(k);
-            for (int k = WU + 1; k_stop == 0; ++k)
-                level(k);
-#endif
-#endif
-#if MM_LG_CHECK_FORM == 3
                 {
                     const unsigned long long m_dead = __ballot(dead), m_first = __ballot(first_ok), m_ok = __ballot(S_s);
-                    m_inv1 = ~m_dead & ~m_first;
-                    m_inv2 = ~m_dead & m_first & ~m_ok;
+                    m_inv1 = ~m_dead & ~m_first;         /* the first leaf was not valid: what the sibling added is undone */
+                    m_inv2 = ~m_dead & m_first & ~m_ok; /* the pair's subtree turned: it does not wait, it returns */
                     if (__builtin_expect((m_inv1 | m_inv2) != 0ull, 0)) {
                         slow = true;
                         break;
@@ -1300,39 +1141,6 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
             if (leaf >= n_leaves)
                 break;
         }
-#else
-#ifndef MM_LG_EXP_NO_RETIRE
-#if MM_LG_CHECK_FORM == 2
-            {
-                const unsigned long long m_dead = __ballot(dead), m_first = __ballot(first_ok), m_ok = __ballot(S_s);
-                const unsigned long long m_inv1 = ~m_dead & ~m_first, m_inv2 = ~m_dead & m_first & ~m_ok;
-                if (__builtin_expect((m_inv1 | m_inv2) != 0ull, 0)) {
-                    const bool inv1 = ((m_inv1 >> L.lane) & 1ull) != 0ull, inv2 = ((m_inv2 >> L.lane) & 1ull) != 0ull;
-#else
-            {
-                const bool inv1 = !dead && !first_ok;       /* the first leaf was not valid: what the sibling added is undone */
-                const bool inv2 = !dead && first_ok && !S_s; /* the pair's subtree turned: it does not wait, it returns */
-#if MM_LG_CHECK_FORM == 1
-                if (__builtin_expect(__ballot(inv1 || inv2) != 0ull, 0)) {
-#else
-                if (__ballot(inv1 || inv2) != 0ull) {
-#endif
-#endif
-                    if (inv1) {
-                        S_n = P_n;
-                        S_nalpha = P_nalpha;
-                        S_alpha = P_alpha; /* min(1, exp(d)) of the first leaf */
-                        lf -= 1u;          /* the sibling's leapfrog step was not the chain's */
-                    }
-                    retire(leaf, 1, inv1);
-                    retire(lf1, k_stop + 1, inv2);
-                }
-            }
-#endif
-            if (k_stop >= j)
-                break; /* reached the doubling's own level: complete */
-        }
-#endif
         MM_LG_TICK(L, 2); /* tools/lg_profile.py: the whole lean loop lands in section 2 */
         if (died) {
             S_n = F_n;
@@ -1411,25 +1219,9 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
             walk_up(leaf | 1u);
             return true;
         };
-#if MM_LG_PAIR_UNROLL
-        /* two pairs per trip: the leaf index modulo 4 is a constant in each copy (which leaf files a first-leaf record,
-         * whether level 1 merges or waits) */
-        if (j == 1) {
-            (void)leaf_pair(0u);
-        } else {
-            for (unsigned int leaf4 = 0; leaf4 < n_leaves; leaf4 += 4) {
-                const unsigned int base = leaf4 & ~3u;
-                if (!leaf_pair(base))
-                    break;
-                if (!leaf_pair(base | 2u))
-                    break;
-            }
-        }
-#else
         for (unsigned int leaf = 0; leaf < n_leaves; leaf += 2)
             if (!leaf_pair(leaf))
                 break;
-#endif
     }
 
     L.n_lf += lf;
@@ -2127,12 +1919,10 @@ __global__ __launch_bounds__(OCC == 2 ? 512 : 64, OCC == 2 ? 2 : 1) void mm_nuts
             keep = false;
         }
         MM_LGQ_T(0);
-#if MM_LG_UNIFORM_J
         /* the queue (= the level of the unit) is the same in all 64 lanes by construction: say so, and everything derived from it
          * -- the kind of unit, the doublings it runs, the hand-over's queue -- is scalar control flow (mm_lg_doubling, round 6) */
         qi = __builtin_amdgcn_readfirstlane(qi);
         shard = __builtin_amdgcn_readfirstlane(shard);
-#endif
         if (quit || qi < 0)
             break;
         const bool use_keep = n_keep > 0u && !give_back; /* wave-uniform; then qi == keep_q in the own shard */

@@ -558,16 +558,6 @@ __global__ __launch_bounds__(64) void mm_half_chain_tile_kernel(const T *__restr
             }
         }
     };
-#ifdef MM_STATS_DEPHASE /* experiment hook of tools/stats_probe.hip: which waves start late, and by how many 64-cycle units */
-    {
-        const unsigned int sel = MM_STATS_DEPHASE == 1 ? (blockIdx.x & 1u)
-                               : MM_STATS_DEPHASE == 2 ? (blockIdx.x >= gridDim.x / 2 ? 1u : 0u)
-                               : MM_STATS_DEPHASE == 3 ? ((blockIdx.x >> 8) & 1u)
-                               : ((blockIdx.x >> 2) & 1u);
-        if (sel)
-            __builtin_amdgcn_s_sleep(MM_STATS_DEPHASE_UNITS);
-    }
-#endif
     if (prefetch && blockIdx.x < n_half)
         request(blockIdx.x);
     for (unsigned long long hc = blockIdx.x; hc < n_half; hc += gridDim.x) {
@@ -607,7 +597,6 @@ __global__ __launch_bounds__(64) void mm_half_chain_tile_kernel(const T *__restr
         /* mean, centred sum of squares, centring in place, up to four parameters at a time in one basic block: their LDS
          * reads and wave reductions are independent chains the scheduler interleaves (one parameter after the other, two
          * waves per SIMD, every DPP / readlane / LDS latency was exposed: 0.10 of the kernel's 0.39 ms) */
-#ifndef MM_STATS_PROBE_SKIP_CENTER
         auto centre = [&](unsigned int d0, auto nu_tag) __attribute__((always_inline)) {
             constexpr unsigned int NU = decltype(nu_tag)::value;
             float s0[NU], mean[NU], q[NU];
@@ -656,7 +645,6 @@ __global__ __launch_bounds__(64) void mm_half_chain_tile_kernel(const T *__restr
             else
                 centre(d0, std::integral_constant<unsigned int, 1>());
         }
-#endif
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         /* the tiles, software-pipelined: the operands of tile sl + 1 are requested before the 128 multiply-adds of tile
@@ -682,7 +670,6 @@ __global__ __launch_bounds__(64) void mm_half_chain_tile_kernel(const T *__restr
                 yw[b][4 * i + 3] = v[3];
             }
         };
-#ifndef MM_STATS_PROBE_SKIP_TILES /* measurement aid of tools/stats_probe.hip; never defined in the library build */
         fetch(0, 0);
 #pragma unroll
         for (int sl = 0; sl < TPL; ++sl) {
@@ -695,7 +682,6 @@ __global__ __launch_bounds__(64) void mm_half_chain_tile_kernel(const T *__restr
                 for (unsigned int j = 0; j < SK; ++j)
                     acc[sl][j] = fmaf(yt[b][r], yw[b][r + j], acc[sl][j]);
         }
-#endif
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
@@ -948,7 +934,7 @@ __device__ __forceinline__ void mm_load_dt(const T *p, float (&out)[DT])
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                                      \
     } while (0)
 
-template <class T, int R1, int DT, int WPE, bool TWL, bool TOP>
+template <class T, int R1, int DT, int WPE, bool TOP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void mm_chain_fft_kernel(const T *__restrict__ sample, unsigned long long C, unsigned int n, unsigned int D, unsigned int m,
                          unsigned int n_pt, const mm_cx *__restrict__ tw, float *__restrict__ means,
@@ -963,37 +949,18 @@ void mm_chain_fft_kernel(const T *__restrict__ sample, unsigned long long C, uns
     const unsigned int d0 = pt * DT + DT <= D ? pt * DT : D - DT;
     const unsigned long long Wt = 4ull * n_wg;
 
-    /* twiddles: in registers (2 (R1 + 6) of them), or -- TWL -- one copy per workgroup in LDS behind the exchange blocks,
-     * read where they are used (R1 + 6 more ds_read_b64 per transform, conflict-free: lane-contiguous) */
-    mm_cx tw1[TWL ? 1 : R1], tw2[TWL ? 1 : 8];
-    const mm_cx *twl = reinterpret_cast<const mm_cx *>(lds_raw) + 4 * pl::LDS_CX;
-    if constexpr (TWL) {
-        mm_cx *twl_w = reinterpret_cast<mm_cx *>(lds_raw) + 4 * pl::LDS_CX;
-        for (unsigned int i = threadIdx.x; i < R1 * 64u + 64u; i += 256u)
-            twl_w[i] = tw[i];
-        __syncthreads();
-    } else {
+    /* twiddles: in registers (2 (R1 + 6) of them) */
+    mm_cx tw1[R1], tw2[8];
 #pragma unroll
-        for (int b = 1; b < R1; ++b)
-            tw1[b] = tw[b * 64 + lane];
-        tw1[0] = mm_cx{1.f, 0.f};
+    for (int b = 1; b < R1; ++b)
+        tw1[b] = tw[b * 64 + lane];
+    tw1[0] = mm_cx{1.f, 0.f};
 #pragma unroll
-        for (int g = 1; g < 8; ++g)
-            tw2[g] = tw[R1 * 64 + g * 8 + (lane & 7u)];
-        tw2[0] = mm_cx{1.f, 0.f};
-    }
-    auto tw1_of = [&](int b) -> mm_cx {
-        if constexpr (TWL)
-            return twl[b * 64 + lane];
-        else
-            return tw1[b];
-    };
-    auto tw2_of = [&](int g) -> mm_cx {
-        if constexpr (TWL)
-            return twl[R1 * 64 + g * 8 + (lane & 7u)];
-        else
-            return tw2[g];
-    };
+    for (int g = 1; g < 8; ++g)
+        tw2[g] = tw[R1 * 64 + g * 8 + (lane & 7u)];
+    tw2[0] = mm_cx{1.f, 0.f};
+    auto tw1_of = [&](int b) -> mm_cx { return tw1[b]; };
+    auto tw2_of = [&](int g) -> mm_cx { return tw2[g]; };
 
     /* TOP: the host found 64 (H - 1) < m, so only the last of a lane's H points can lie in the padding -- the others need
      * no select (a select on a lane mask costs two issue slots: tools/xlane_rate.hip) */
@@ -1112,41 +1079,33 @@ void mm_chain_fft_kernel(const T *__restrict__ sample, unsigned long long C, uns
         out[i] = acc[i];
 }
 
-/* ---- half-chains longer than 1024 draws (n_collect > 2048): the same power spectrum, the transform cut in two --------------
- * N = N1 x 2048 >= 2 m.  With t = n2 + 2048 n1 and f = k1 + N1 k2 (Cooley-Tukey),
- *     Z[k1 + N1 k2] = sum_{n2 < 2048} w_2048^(n2 k2) . [ w_N^(n2 k1) . sum_{n1 < N1 / 2} z[n2 + 2048 n1] w_N1^(n1 k1) ]
- * (the upper half of n1 is the zero padding): for every residue k1 a short sum over n1 per point, a twiddle, and the
- * wave-level 2048-point transform of mm_stats_fft.h (all of whose inputs are data now: mm_fft_pass1_full).  One wave per
- * workgroup takes the chains wg, wg + n_wg, ... of ONE parameter; its power spectrum S[N] lives in LDS (bins in natural
- * order) and leaves as one slab [N] at the end: the tail kernel and the inverse are shared with the short-chain path.
- * The chain is read N1 + 1 times (once for the means), from L2 after the first: this path is for samples whose direct
- * lag sums would cost m^2 (a [65536, 4000, 3] sample: 406 ms through the direct kernel, and no kernel at all beyond
- * m = 6800 at D = 3, where its LDS layout ends).  N <= 32768: m <= 16384. */
-#ifndef MM_STATS_LONG_PREFETCH
-#define MM_STATS_LONG_PREFETCH 1
-#endif
-template <class T, int N1, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void mm_chain_fft_long_kernel(const T *__restrict__ sample, unsigned long long C, unsigned int n,
+/* ---- half-chains of 1025 .. 2048 draws (2048 < n_collect <= 4096): the same power spectrum, the transform cut in two -------
+ * N = 4096 = 2 x 2048 >= 2 m.  With t = n2 + 2048 n1 and f = k1 + 2 k2 (Cooley-Tukey), the upper half of the input being the
+ * zero padding (only n1 = 0 carries data),
+ *     Z[k1 + 2 k2] = sum_{n2 < 2048} w_2048^(n2 k2) . [ w_4096^(n2 k1) . z[n2] ]
+ * for the two residues k1: a twiddle per point and the wave-level 2048-point transform of mm_stats_fft.h (all of whose
+ * inputs are data now: mm_fft_pass1_full).  Workgroup = ONE wave, which takes the chains wg, wg + n_wg, ... of ONE
+ * parameter; its power spectrum S[4096] lives in LDS (bins in natural order) and leaves as one slab [N] at the end: the
+ * tail kernel and the inverse are shared with the short-chain path.  A lane's 32 points of both half-chains stay in its
+ * registers, so the chain is read ONCE -- the means and both residue passes take their points from there (read three times,
+ * [65536, 4000, 3] took 4.0 ms instead of 3.3; through the direct lag sums, which cost m^2, 406 ms).  Longer half-chains go
+ * to mm_chain_fft_res_kernel below, which keeps the spectrum in registers. */
+template <class T>
+__global__ __launch_bounds__(64) void mm_chain_fft_long_kernel(const T *__restrict__ sample, unsigned long long C, unsigned int n,
                                                                unsigned int D, unsigned int m, unsigned int n_wg,
                                                                const mm_cx *__restrict__ tw, const mm_cx *__restrict__ wN,
                                                                float *__restrict__ means, float *__restrict__ ssq,
                                                                float *__restrict__ slabs)
 {
-    constexpr int R1 = 32, HALF = N1 / 2;
-    constexpr unsigned int N = 2048u * N1;
-    /* loads are issued in batches of AC x HALF x 2 before any is used: one at a time (a dependent load per point) the kernel
-     * waited out a memory latency per point -- 11.9 ms for [65536, 4000, 3] */
-    constexpr int AC = HALF >= 8 ? 4 : 8;
+    /* HALF = data blocks of 2048 draws per half-chain.  The general cut sums over them; here there is one, and the
+     * loops over n1 < HALF, the per-batch copies r0 / r1 and the wave index (0: one wave) below are what is left of the general
+     * form.  They cost nothing and they stay: the optimiser's output follows the order in which the source states things,
+     * and this kernel's machine code is kept instruction for instruction (tools/codeobj_diff.py). */
+    constexpr int R1 = 32, HALF = 1;
+    constexpr unsigned int N = 4096u;
+    constexpr int AC = 8; /* the twiddles w_N^(n2 k1) of AC points are requested before any of them is used */
     using pl = mm_fft_plan<R1>;
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];
-    /* WAVES > 1 (round 5, N1 = 4 and 8): the residues k1 of a chain are dealt to the waves of the workgroup (k1 = wave, wave +
-     * WAVES, ...), which share ONE spectrum S[N] -- the bins k1 + N1 k2 of different residues are different words, so no two waves
-     * ever meet and S needs no synchronisation between the first and the last barrier of the launch -- and each have their own
-     * exchange block.  With one wave per workgroup the 64 KB spectrum of N1 = 8 left one wave per CU (S is what fills the LDS);
-     * four waves beside one S are four per CU, and each reads the chain N1 / WAVES + 1 / WAVES times instead of N1 + 1. */
-    static_assert(WAVES == 1 || N1 % WAVES == 0, "residues are dealt evenly");
-    static_assert(N1 != 4 || WAVES > 1, "the staged column becomes visible at the barrier of the means");
-    __shared__ float msum[2][WAVES][2]; /* the waves' shares of the two half-chains' sums, by chain parity */
     const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     float *const S = lds_raw;                                        /* [N] */
     mm_cx *const lds = reinterpret_cast<mm_cx *>(lds_raw + N) + (size_t)wave * pl::LDS_CX; /* the wave's exchange block */
@@ -1164,177 +1123,80 @@ __global__ __launch_bounds__(64 * WAVES) void mm_chain_fft_long_kernel(const T *
         d = blockIdx.x % D;
         wg = blockIdx.x / D;
     }
-    for (unsigned int i = threadIdx.x; i < N; i += 64u * WAVES)
+    for (unsigned int i = threadIdx.x; i < N; i += 64u)
         S[i] = 0.f;
-    if constexpr (WAVES > 1)
-        __syncthreads();
-    else
-        MM_WAVE_LDS_SYNC();
+    MM_WAVE_LDS_SYNC();
     auto tw1_of = [&](int b) -> mm_cx { return tw[b * 64 + lane]; };
     auto tw2_of = [&](int g) -> mm_cx { return tw[R1 * 64 + g * 8 + (lane & 7u)]; };
     const size_t second = (size_t)(n - m) * D; /* the second half-chain: rows [n - m, n) */
     const float inv_m = 1.0f / (float)m;
-    /* N1 = 2 (half-chains up to 2048 draws): a lane's R1 points of both half-chains stay in its registers, so the chain is
-     * read ONCE -- the means and both residue passes take their points from there -- instead of three times (round 5:
-     * [65536, 4000, 3] 4.0 -> 3.3 ms).  At N1 = 4 the 128 cached values per lane made the kernel SLOWER ([65536, 8000, 3]
-     * 13.4 -> 19.4 ms): kept to N1 = 2 */
-    constexpr bool CACHE = HALF == 1;
-    /* N1 = 4 (half-chains of 2049 .. 4096 draws): the parameter's column of both half-chains is STAGED in LDS once per chain
-     * (32 KB beside the 32 KB spectrum), by the pass that sums it for the means, and the four residue passes read it from there:
-     * from the L2 every pass pulled the chain's lines again -- all D parameters of them, 75 GB at [65536, 8000, 3] -- and the
-     * kernel sat at the L2's bandwidth whatever its occupancy. */
-    constexpr bool STAGE = N1 == 4;
-    float *const st0 = lds_raw + N + (size_t)WAVES * 2 * pl::LDS_CX, *const st1 = st0 + N / 2;
-    unsigned int parity = 0;
-    /* N1 = 2: the NEXT chain's points are requested before this chain's two transforms and arrive behind them (one wave per
-     * SIMD has nobody to hide a memory latency behind; the second set of 64 registers is there) */
-    float nx0[CACHE ? R1 : 1][CACHE ? HALF : 1], nx1[CACHE ? R1 : 1][CACHE ? HALF : 1];
-    auto fetch = [&](unsigned long long cc, float (&f0)[CACHE ? R1 : 1][CACHE ? HALF : 1], float (&f1)[CACHE ? R1 : 1][CACHE ? HALF : 1])
+    /* the NEXT chain's points are requested before this chain's two transforms and arrive behind them (one wave per SIMD has
+     * nobody to hide a memory latency behind; the second set of 64 registers is there) */
+    float nx0[R1][HALF], nx1[R1][HALF];
+    auto fetch = [&](unsigned long long cc, float (&f0)[R1][HALF], float (&f1)[R1][HALF])
                      __attribute__((always_inline)) {
         const T *const b = sample + (size_t)cc * n * D + d;
 #pragma unroll
-        for (int a = 0; a < (CACHE ? R1 : 1); ++a)
+        for (int a = 0; a < R1; ++a)
 #pragma unroll
-            for (int n1 = 0; n1 < (CACHE ? HALF : 1); ++n1) {
+            for (int n1 = 0; n1 < HALF; ++n1) {
                 const unsigned int t = 64u * a + lane + 2048u * n1, tc = t < m ? t : m - 1u;
                 f0[a][n1] = (float)b[(size_t)tc * D];
                 f1[a][n1] = (float)b[second + (size_t)tc * D];
             }
     };
-    if constexpr (CACHE && MM_STATS_LONG_PREFETCH)
-        if (wg < C)
-            fetch(wg, nx0, nx1);
-    for (unsigned long long c = wg; c < C; c += n_wg, parity ^= 1u) {
-        const T *const base = sample + (size_t)c * n * D + d;
+    if (wg < C)
+        fetch(wg, nx0, nx1);
+    for (unsigned long long c = wg; c < C; c += n_wg) {
         float s0 = 0.f, s1 = 0.f;
-        float c0[CACHE ? R1 : 1][CACHE ? HALF : 1], c1[CACHE ? R1 : 1][CACHE ? HALF : 1];
-        if constexpr (CACHE) {
-            if constexpr (MM_STATS_LONG_PREFETCH) {
+        float c0[R1][HALF], c1[R1][HALF];
 #pragma unroll
-                for (int a = 0; a < R1; ++a)
+        for (int a = 0; a < R1; ++a)
 #pragma unroll
-                    for (int n1 = 0; n1 < HALF; ++n1) {
-                        c0[a][n1] = nx0[a][n1];
-                        c1[a][n1] = nx1[a][n1];
-                    }
-                if (c + n_wg < C)
-                    fetch(c + n_wg, nx0, nx1);
-            } else
-#pragma unroll
-            for (int a = 0; a < R1; ++a)
-#pragma unroll
-                for (int n1 = 0; n1 < HALF; ++n1) {
-                    const unsigned int t = 64u * a + lane + 2048u * n1, tc = t < m ? t : m - 1u;
-                    c0[a][n1] = (float)base[(size_t)tc * D];
-                    c1[a][n1] = (float)base[second + (size_t)tc * D];
-                }
-            /* the same summation order as the strided pass below: t = lane + 64 i ascending per lane, i.e. n1-major */
-#pragma unroll
-            for (int n1 = 0; n1 < HALF; ++n1)
-#pragma unroll
-                for (int a = 0; a < R1; ++a) {
-                    const bool in = 64u * a + lane + 2048u * n1 < m;
-                    s0 += in ? c0[a][n1] : 0.f;
-                    s1 += in ? c1[a][n1] : 0.f;
-                }
-        } else {
-        if constexpr (STAGE)
-            __syncthreads(); /* the last chain's residue passes have read the staged column */
-        for (unsigned int t0 = lane + 64u * 8u * wave; t0 < m; t0 += 64u * 8u * WAVES) {
-            float u0[8], u1[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const unsigned int t = t0 + 64u * u, tc = t < m ? t : m - 1u;
-                u0[u] = (float)base[(size_t)tc * D];
-                u1[u] = (float)base[second + (size_t)tc * D];
+            for (int n1 = 0; n1 < HALF; ++n1) {
+                c0[a][n1] = nx0[a][n1];
+                c1[a][n1] = nx1[a][n1];
             }
+        if (c + n_wg < C)
+            fetch(c + n_wg, nx0, nx1);
+        /* summation order: t = lane + 64 a ascending per lane */
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const bool in = t0 + 64u * u < m;
-                s0 += in ? u0[u] : 0.f;
-                s1 += in ? u1[u] : 0.f;
-                if constexpr (STAGE) {
-                    if (in) {
-                        st0[t0 + 64u * u] = u0[u];
-                        st1[t0 + 64u * u] = u1[u];
-                    }
-                }
+        for (int n1 = 0; n1 < HALF; ++n1)
+#pragma unroll
+            for (int a = 0; a < R1; ++a) {
+                const bool in = 64u * a + lane + 2048u * n1 < m;
+                s0 += in ? c0[a][n1] : 0.f;
+                s1 += in ? c1[a][n1] : 0.f;
             }
-        }
-        }
         float t0s = wave_sum_dpp_bcast(s0), t1s = wave_sum_dpp_bcast(s1);
-        if constexpr (WAVES > 1 && !CACHE) { /* (a wave that caches the chain has summed all of it itself) */
-            /* every wave summed its share of the time steps: the shares meet in LDS and are added in wave order.  One barrier
-             * per chain (the buffer alternates with the chain's parity: a wave two chains ahead cannot exist, it would have had
-             * to pass the barrier in between) */
-            if (lane == 0u) {
-                msum[parity][wave][0] = t0s;
-                msum[parity][wave][1] = t1s;
-            }
-            __syncthreads();
-            t0s = msum[parity][0][0];
-            t1s = msum[parity][0][1];
-#pragma unroll
-            for (int w2 = 1; w2 < WAVES; ++w2) {
-                t0s += msum[parity][w2][0];
-                t1s += msum[parity][w2][1];
-            }
-        }
         const float mu0 = t0s * inv_m, mu1 = t1s * inv_m;
         float q0 = 0.f, q1 = 0.f;
-        for (unsigned int k1 = wave; k1 < (unsigned int)N1; k1 += (unsigned int)WAVES) {
-            /* The offsets of a lane's R1 x HALF points (and their in-range masks, and the twiddle indices) depend on neither the
-             * chain nor the residue, and the compiler, left to itself, computes them all ONCE before the chain loop and keeps
-             * them: hundreds of 64-bit values it has no registers for (N1 = 8: 2.4 KB of scratch per lane, 245 spill stores
-             * ahead of the loop and a scratch reload in front of every load of the sample -- a residue pass took eleven times
-             * what it takes at N1 = 2; 4.9 KB at N1 = 16).  An opaque copy of the lane index per residue makes them cheap
-             * arithmetic again, done where it is used. */
-            unsigned int lane_k = lane;
-            if constexpr (N1 == 4 || N1 == 8) /* N1 = 16 is faster with the spilled table than with the arithmetic (307 vs 381 ms) */
-                asm volatile("" : "+v"(lane_k));
-            const mm_cx *wNk = wN;
-            mm_cx w1[HALF]; /* w_N1^(n1 k1) */
-#pragma unroll
-            for (int n1 = 0; n1 < HALF; ++n1)
-                w1[n1] = wNk[(((unsigned int)n1 * k1) & (unsigned int)(N1 - 1)) * 2048u];
+        for (unsigned int k1 = wave; k1 < 2u; ++k1) {
+            const mm_cx w1 = wN[0]; /* w_2^(n1 k1) at n1 = 0 */
             mm_cx y[R1];
 #pragma unroll
             for (int a0 = 0; a0 < R1; a0 += AC) {
-                float r0[AC][HALF], r1[AC][HALF];
+                float r0[AC], r1[AC];
                 mm_cx wt[AC];
 #pragma unroll
                 for (int aa = 0; aa < AC; ++aa) {
-                    const unsigned int n2 = 64u * (a0 + aa) + lane_k;
-                    wt[aa] = wNk[(n2 * k1) & (N - 1u)]; /* w_N^(n2 k1) */
-#pragma unroll
-                    for (int n1 = 0; n1 < HALF; ++n1) {
-                        if constexpr (CACHE) {
-                            r0[aa][n1] = c0[a0 + aa][n1];
-                            r1[aa][n1] = c1[a0 + aa][n1];
-                        } else if constexpr (STAGE) {
-                            r0[aa][n1] = st0[n2 + 2048u * n1]; /* t < N / 2: inside the block; beyond m masked below */
-                            r1[aa][n1] = st1[n2 + 2048u * n1];
-                        } else {
-                            const unsigned int t = n2 + 2048u * n1, tc = t < m ? t : m - 1u;
-                            r0[aa][n1] = (float)base[(size_t)tc * D];
-                            r1[aa][n1] = (float)base[second + (size_t)tc * D];
-                        }
-                    }
+                    const unsigned int n2 = 64u * (a0 + aa) + lane;
+                    wt[aa] = wN[(n2 * k1) & (N - 1u)]; /* w_N^(n2 k1) */
+                    r0[aa] = c0[a0 + aa][0];
+                    r1[aa] = c1[a0 + aa][0];
                 }
 #pragma unroll
                 for (int aa = 0; aa < AC; ++aa) {
-                    const unsigned int n2 = 64u * (a0 + aa) + lane_k;
-                    mm_cx acc = mm_cx{0.f, 0.f};
-#pragma unroll
-                    for (int n1 = 0; n1 < HALF; ++n1) {
-                        const bool in = n2 + 2048u * n1 < m;
-                        const mm_cx v = mm_cx{in ? r0[aa][n1] - mu0 : 0.f, in ? r1[aa][n1] - mu1 : 0.f};
-                        if (k1 == 0u) { /* every point passes here exactly once per k1 */
-                            q0 = fmaf(v.re, v.re, q0);
-                            q1 = fmaf(v.im, v.im, q1);
-                        }
-                        acc = mm_cx_add(acc, mm_cx_mul(v, w1[n1].re, w1[n1].im));
+                    const unsigned int n2 = 64u * (a0 + aa) + lane;
+                    const bool in = n2 < m;
+                    const mm_cx v = mm_cx{in ? r0[aa] - mu0 : 0.f, in ? r1[aa] - mu1 : 0.f};
+                    if (k1 == 0u) { /* every point passes here exactly once per k1 */
+                        q0 = fmaf(v.re, v.re, q0);
+                        q1 = fmaf(v.im, v.im, q1);
                     }
+                    /* the sum over the data blocks has ONE term: 0 + v w_2^0 with the table's w_2^0, as the general cut
+                     * forms it, so the bits stay what they were (a -0 becomes +0) */
+                    const mm_cx acc = mm_cx_add(mm_cx{0.f, 0.f}, mm_cx_mul(v, w1.re, w1.im));
                     y[a0 + aa] = mm_cx_mul(acc, wt[aa].re, wt[aa].im);
                 }
             }
@@ -1357,25 +1219,22 @@ __global__ __launch_bounds__(64 * WAVES) void mm_chain_fft_long_kernel(const T *
             for (int j = 0; j < pl::J; ++j)
 #pragma unroll
                 for (int h = 0; h < 8; ++h) {
-                    const unsigned int f = k1 + (unsigned int)N1 * (unsigned int)mm_fft_bin<R1>((int)lane, j, h);
+                    const unsigned int f = k1 + 2u * (unsigned int)mm_fft_bin<R1>((int)lane, j, h);
                     S[f] += Sr[j][h]; /* every (lane, j, h) owns its bin: no two lanes meet */
                 }
         }
         q0 = wave_sum_dpp_bcast(q0);
         q1 = wave_sum_dpp_bcast(q1);
-        if (lane == 0u && wave == 0u) { /* residue 0, where the squares are taken, is wave 0's */
+        if (lane == 0u && wave == 0u) {
             means[(size_t)c * D + d] = mu0;
             means[((size_t)c + (size_t)C) * D + d] = mu1;
             ssq[(size_t)c * D + d] = q0;
             ssq[((size_t)c + (size_t)C) * D + d] = q1;
         }
     }
-    if constexpr (WAVES > 1)
-        __syncthreads();
-    else
-        MM_WAVE_LDS_SYNC();
+    MM_WAVE_LDS_SYNC();
     float *const out = slabs + ((size_t)wg * D + d) * N;
-    for (unsigned int i = threadIdx.x; i < N; i += 64u * WAVES)
+    for (unsigned int i = threadIdx.x; i < N; i += 64u)
         out[i] = S[i];
 }
 
@@ -1861,7 +1720,6 @@ static std::atomic<uint64_t> g_stats_direct_work_limit{1ull << 46};
 struct StatsFftPlan {
     bool use = false;
     int r1 = 0, dt = 0, wpe = 0;
-    bool twl = false;
     unsigned int n_pt = 0, n_wg = 0, N = 0;
 };
 
@@ -1886,11 +1744,6 @@ static StatsFftPlan stats_fft_plan(size_t n_chains, size_t n, size_t dim, int de
     p.n_pt = (unsigned int)((dim + dt_max - 1) / dt_max);
     p.dt = (int)((dim + p.n_pt - 1) / p.n_pt);
     p.wpe = p.r1 == 8 && p.dt <= 3 ? 3 : 2;
-    p.twl = false;
-    if (const char *e = mm_tuning_env("MMCMC_FFT_WPE"))
-        p.wpe = atoi(e);
-    if (const char *e = mm_tuning_env("MMCMC_FFT_TWL"))
-        p.twl = atoi(e) != 0;
     /* resident workgroups of four waves: waves per SIMD x CUs, shared between the parameter tiles */
     /* the workgroup count fixes which chains a wave sums in f32, so it must not depend on the device (CU count, partition
      * mode): 256 compute units' worth, an MI355X's, on every device -- R-hat / ESS are then the same bits everywhere */
@@ -1904,19 +1757,16 @@ static StatsFftPlan stats_fft_plan(size_t n_chains, size_t n, size_t dim, int de
     return p;
 }
 
-/* the long-chain path (mm_chain_fft_long_kernel): half-chains of 1025 .. 16384 draws */
+/* the long-chain paths: half-chains of 1025 .. 2048 draws (mm_chain_fft_long_kernel, N1 = 2) and beyond (mm_chain_fft_res_kernel) */
 struct StatsLongPlan {
     bool use = false;
-    bool res = false; /* round 6: one (residue, parameter) per wave, spectrum in registers (mm_chain_fft_res_kernel): N1 >= 4 */
-    unsigned int res_r1 = 32; /* its inner transform: 64 res_r1 points */
-    unsigned int N1 = 0, N = 0, n_wg = 0, waves = 1;
+    bool res = false; /* round 6: one (residue, parameter) per wave, spectrum in registers (mm_chain_fft_res_kernel): N1 >= 3 */
+    unsigned int N1 = 0, N = 0, n_wg = 0;
 };
 constexpr size_t kStatsLongMaxM = 131072; /* N = 2^18: the inverse (mm_fft_finish_long_kernel) is O(m N) per parameter */
-/* LDS of a workgroup of the long-chain kernel: the spectrum, an exchange block per wave, at N1 = 4 the staged column */
-static size_t stats_long_lds(unsigned int N, unsigned int waves, unsigned int N1)
-{
-    return ((size_t)N + (size_t)waves * 2 * (size_t)mm_fft_plan<32>::LDS_CX + (N1 == 4 ? (size_t)N : 0)) * sizeof(float);
-}
+/* LDS of a workgroup of mm_chain_fft_long_kernel: the spectrum S[4096] and the wave's exchange block */
+constexpr size_t kStatsLongLds = ((size_t)4096 + 2 * (size_t)mm_fft_plan<32>::LDS_CX) * sizeof(float);
+static_assert(kStatsLongLds <= 64 * 1024, "mm_chain_fft_long_kernel is launched without raising its dynamic LDS limit");
 static StatsLongPlan stats_long_plan(size_t n_chains, size_t n, size_t dim, int sel_in = -1)
 {
     StatsLongPlan p;
@@ -1928,36 +1778,15 @@ static StatsLongPlan stats_long_plan(size_t n_chains, size_t n, size_t dim, int 
     /* N = 2048 N1 >= 2 m, N1 the SMALLEST such count (round 6, late: it was the next power of two -- but a residue wave reads
      * the whole chain, so time goes as N1 x the data: m = 10 000 took N1 = 16 where 10 do, [16384, 20000, 3] 20.7 -> 9.0 ms, [16384, 40000, 3] 73 -> 31.7) */
     p.N1 = (unsigned int)std::max<size_t>(2, (m + 1023) / 1024);
-#ifdef MMCMC_TUNING
-    bool old_kernels = false, pow2 = mm_tuning_env("MMCMC_STATS_LONG_POW2") != nullptr; /* A / B against the power-of-two cut */
-    if (mm_tuning_env("MMCMC_STATS_LONG_OLD") != nullptr && m <= 16384) /* ... and against round 5's kernels */
-        old_kernels = pow2 = true;
-    if (pow2) {
-        unsigned int q = 2;
-        while (q < p.N1)
-            q *= 2;
-        p.N1 = q;
-    }
-#else
-    const bool old_kernels = false;
-#endif
     p.N = 2048u * p.N1;
-    if (p.N1 >= 3 && !old_kernels) {
+    if (p.N1 >= 3) {
         /* chain groups: as many as keep ONE resident round of one-wave workgroups busy -- one per SIMD by their registers, 1024
          * on an MI355X; the figure is a constant, not a device query, because the group count fixes the f32 summation grouping
          * -- in multiples of 8 (the kernel's XCD mapping), at most 512 */
         p.res = true;
-        /* inner transforms of 2048 points, one wave per SIMD.  (1024 points and two waves per SIMD -- twice the residues, half
-         * the registers; MMCMC_STATS_RES_R1_16 in measurement builds -- is slower throughout: [65536, 8000, 3] 16.8 against 7.7 ms,
-         * [16384, 20000, 3] 31.3 against 20.7: every residue reads the chain again, profiles/r6za_stats_long_timing_r1_16.log) */
-        p.res_r1 = 32;
-#ifdef MMCMC_TUNING
-        if (mm_tuning_env("MMCMC_STATS_RES_R1_16"))
-            p.res_r1 = 16;
-#endif
-        const size_t n1r = (size_t)p.N / (64 * p.res_r1);
-        const size_t per = dim * n1r;
-        size_t g = per > 0 ? (p.res_r1 == 16 ? 2048 : 1024) / per : 8;
+        /* inner transforms of 2048 points, one wave per SIMD: N1 residues per parameter */
+        const size_t per = dim * p.N1;
+        size_t g = per > 0 ? 1024 / per : 8;
         g = std::min<size_t>(512, std::max<size_t>(8, g / 8 * 8));
         p.n_wg = (unsigned int)std::min<size_t>(g, n_chains);
         return p;
@@ -1965,13 +1794,7 @@ static StatsLongPlan stats_long_plan(size_t n_chains, size_t n, size_t dim, int 
     /* device-independent (the workgroup count fixes the f32 summation grouping): at most 512 chain groups, and no more than fit
      * the one-wave workgroups an MI355X holds at once with this kernel's LDS (1024 at N1 = 2: a launch of 1536 ran a second,
      * half-empty round), a multiple of 8 (the kernel's XCD mapping); fewer for few chains */
-    /* waves per workgroup: one where the chain is cached in registers (N1 = 2) and where a second exchange block no longer
-     * fits beside the spectrum (N1 = 16: 128 KB); four at N1 = 8 ([16384, 16000, 3]: 32.8 -> 9.4 ms, with the kernel's spills
-     * gone) and at N1 = 4 (with the column staged in LDS: [65536, 8000, 3] 13.0 -> 12.1 ms; without it one / two / four waves
-     * 15.8 / 13.0 / 14.7 ms) */
-    p.waves = (p.N1 == 8 || p.N1 == 4) ? 4u : 1u;
-    const size_t lds = stats_long_lds(p.N, p.waves, p.N1);
-    const size_t resident = 256 * std::max<size_t>(1, (160u << 10) / lds); /* MI355X: 256 CUs x workgroups per CU by their LDS */
+    const size_t resident = 256 * std::max<size_t>(1, (160u << 10) / kStatsLongLds); /* MI355X: 256 CUs x workgroups per CU by their LDS */
     size_t g = 512;
     if (dim > 0 && g * dim > resident)
         g = std::max<size_t>(8, resident / dim / 8 * 8);
@@ -2060,22 +1883,22 @@ static const mm_cx *stats_fft_twiddles(int device, int r1)
     return d;
 }
 
-template <class T, int R1, int DT, int WPE, bool TWL, bool TOP>
+template <class T, int R1, int DT, int WPE, bool TOP>
 static int stats_fft_launch1(const StatsFftPlan &p, const void *sample, size_t n_chains, size_t n, size_t dim, size_t m,
                              const mm_cx *tw, float *means, float *ssq, float *slabs, hipStream_t stream)
 {
-    const size_t lds = ((size_t)4 * mm_fft_plan<R1>::LDS_CX + (TWL ? R1 * 64 + 64 : 0)) * sizeof(mm_cx);
+    const size_t lds = (size_t)4 * mm_fft_plan<R1>::LDS_CX * sizeof(mm_cx);
     if (lds > 64 * 1024) {
         static std::atomic<unsigned long long> attr_set{0};
         int dev = 0;
         (void)hipGetDevice(&dev);
         if (!(attr_set.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
-            MM_HIP(hipFuncSetAttribute((const void *)mm_chain_fft_kernel<T, R1, DT, WPE, TWL, TOP>,
+            MM_HIP(hipFuncSetAttribute((const void *)mm_chain_fft_kernel<T, R1, DT, WPE, TOP>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             attr_set.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
         }
     }
-    hipLaunchKernelGGL((mm_chain_fft_kernel<T, R1, DT, WPE, TWL, TOP>), dim3(p.n_wg * p.n_pt), dim3(256), lds, stream,
+    hipLaunchKernelGGL((mm_chain_fft_kernel<T, R1, DT, WPE, TOP>), dim3(p.n_wg * p.n_pt), dim3(256), lds, stream,
                        (const T *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim,
                        (unsigned int)m, p.n_pt, tw, means, ssq, slabs);
     return MMCMC_OK;
@@ -2086,25 +1909,18 @@ static int stats_fft_launch(const StatsFftPlan &p, const void *sample, size_t n_
                             const mm_cx *tw, float *means, float *ssq, float *slabs, hipStream_t stream)
 {
     const bool top = m > 64 * (size_t)(p.r1 / 2 - 1); /* only a lane's last point can be padding */
-#define MM_FFT_CASE(R1V, DTV, WPEV, TWLV)                                                                           \
-    if (p.r1 == R1V && p.dt == DTV && p.wpe == WPEV && p.twl == TWLV)                                               \
-    return top ? stats_fft_launch1<T, R1V, DTV, WPEV, TWLV, true>(p, sample, n_chains, n, dim, m, tw, means, ssq, slabs, stream) \
-               : stats_fft_launch1<T, R1V, DTV, WPEV, TWLV, false>(p, sample, n_chains, n, dim, m, tw, means, ssq, slabs, stream)
-    MM_FFT_CASE(8, 1, 3, false);
-    MM_FFT_CASE(8, 2, 3, false);
-    MM_FFT_CASE(8, 3, 3, false);
-    MM_FFT_CASE(8, 4, 2, false);
-    MM_FFT_CASE(16, 1, 2, false);
-    MM_FFT_CASE(16, 2, 2, false);
-    MM_FFT_CASE(16, 3, 2, false);
-    MM_FFT_CASE(32, 1, 2, false);
-#ifdef MMCMC_TUNING /* experiments: MMCMC_FFT_WPE, MMCMC_FFT_TWL */
-    MM_FFT_CASE(8, 3, 4, false);
-    MM_FFT_CASE(8, 3, 4, true);
-    MM_FFT_CASE(8, 3, 3, true);
-    MM_FFT_CASE(16, 3, 3, true);
-    MM_FFT_CASE(16, 3, 2, true);
-#endif
+#define MM_FFT_CASE(R1V, DTV, WPEV)                                                                                 \
+    if (p.r1 == R1V && p.dt == DTV && p.wpe == WPEV)                                                                \
+    return top ? stats_fft_launch1<T, R1V, DTV, WPEV, true>(p, sample, n_chains, n, dim, m, tw, means, ssq, slabs, stream) \
+               : stats_fft_launch1<T, R1V, DTV, WPEV, false>(p, sample, n_chains, n, dim, m, tw, means, ssq, slabs, stream)
+    MM_FFT_CASE(8, 1, 3);
+    MM_FFT_CASE(8, 2, 3);
+    MM_FFT_CASE(8, 3, 3);
+    MM_FFT_CASE(8, 4, 2);
+    MM_FFT_CASE(16, 1, 2);
+    MM_FFT_CASE(16, 2, 2);
+    MM_FFT_CASE(16, 3, 2);
+    MM_FFT_CASE(32, 1, 2);
 #undef MM_FFT_CASE
     return MMCMC_ERR_UNSUPPORTED;
 }
@@ -2205,20 +2021,15 @@ static int stats_partials_impl(const void *sample, int dtype, size_t n_chains, s
             MM_HIP(hipMallocAsync((void **)&ws, (slab_floats + part_floats + p_floats) * sizeof(float), stream));
         float *bins = ws + slab_floats;
         double *P = reinterpret_cast<double *>(ws + ((slab_floats + part_floats + 1) / 2) * 2);
-        const size_t lds = stats_long_lds(lp.N, lp.waves, lp.N1);
         const unsigned int grid = lp.n_wg * (unsigned int)dim;
-        hipError_t le = hipSuccess;
         if (lp.res) {
             /* means by a streaming pass (dim <= 16: 64 dim threads per half-chain; wider samples through the any-length moments
              * kernel), then one wave per (chain group, residue, parameter) */
-            const unsigned int n1r = lp.N / (64u * lp.res_r1);
+            const unsigned int n1r = lp.N1;
             if ((uint64_t)2 * n_chains >= (1ull << 31) || (uint64_t)lp.n_wg * dim * n1r >= (1ull << 31))
                 return MMCMC_ERR_SHAPE;
             const unsigned int g_mean = (unsigned int)(2 * n_chains), g_res = lp.n_wg * (unsigned int)dim * n1r;
-            const size_t lds_res = (size_t)(lp.res_r1 == 16 ? mm_fft_plan<16>::LDS_CX : mm_fft_plan<32>::LDS_CX) * sizeof(mm_cx);
-            const mm_cx *tw_res = lp.res_r1 == 16 ? stats_fft_twiddles(device, 16) : tw;
-            if (!tw_res)
-                return (int)hipErrorOutOfMemory;
+            const size_t lds_res = (size_t)mm_fft_plan<32>::LDS_CX * sizeof(mm_cx);
 #define MM_RES_LAUNCH(TT)                                                                                           \
     do {                                                                                                            \
         if (dim <= 16)                                                                                              \
@@ -2229,14 +2040,9 @@ static int stats_partials_impl(const void *sample, int dtype, size_t n_chains, s
             hipLaunchKernelGGL(mm_half_chain_moments_any_kernel<TT>, dim3(g_mean * (unsigned int)dim), dim3(64), 0, stream, \
                                (const TT *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, \
                                (unsigned int)m, means, ssq);                                                        \
-        if (lp.res_r1 == 16)                                                                                        \
-            hipLaunchKernelGGL((mm_chain_fft_res_kernel<TT, 16, 2, 2>), dim3(g_res), dim3(64), lds_res, stream, (const TT *)sample, \
-                               (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, n1r, \
-                               lp.n_wg, tw_res, wN, means, ssq, ws);                                                \
-        else                                                                                                        \
-            hipLaunchKernelGGL((mm_chain_fft_res_kernel<TT, 32, 2, 1>), dim3(g_res), dim3(64), lds_res, stream, (const TT *)sample, \
-                               (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, n1r, \
-                               lp.n_wg, tw_res, wN, means, ssq, ws);                                                \
+        hipLaunchKernelGGL((mm_chain_fft_res_kernel<TT, 32, 2, 1>), dim3(g_res), dim3(64), lds_res, stream, (const TT *)sample, \
+                           (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, n1r,  \
+                           lp.n_wg, tw, wN, means, ssq, ws);                                                        \
     } while (0)
             if (dim > 16 && (uint64_t)2 * n_chains * dim >= (1ull << 31))
                 return MMCMC_ERR_SHAPE;
@@ -2246,37 +2052,16 @@ static int stats_partials_impl(const void *sample, int dtype, size_t n_chains, s
                 MM_RES_LAUNCH(double);
 #undef MM_RES_LAUNCH
         } else {
-#define MM_LONG_LAUNCH(TT, NN, WW)                                                                                  \
-    do {                                                                                                            \
-        if (lds > 64 * 1024)                                                                                        \
-            le = hipFuncSetAttribute((const void *)mm_chain_fft_long_kernel<TT, NN, WW>,                            \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        if (le == hipSuccess)                                                                                       \
-            hipLaunchKernelGGL((mm_chain_fft_long_kernel<TT, NN, WW>), dim3(grid), dim3(64 * WW), lds, stream,      \
-                               (const TT *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, \
-                               (unsigned int)m, lp.n_wg, tw, wN, means, ssq, ws);                                   \
-    } while (0)
-#ifdef MMCMC_TUNING /* round 5's kernels for N1 = 4, 8, 16: measurement builds only (MMCMC_STATS_LONG_OLD) */
-#define MM_LONG_PICK(TT)                                                                                            \
-    do {                                                                                                            \
-        switch (lp.N1) {                                                                                            \
-        case 2: MM_LONG_LAUNCH(TT, 2, 1); break;                                                                    \
-        case 4: MM_LONG_LAUNCH(TT, 4, 4); break;                                                                    \
-        case 8: MM_LONG_LAUNCH(TT, 8, 4); break;                                                                    \
-        default: MM_LONG_LAUNCH(TT, 16, 1); break;                                                                  \
-        }                                                                                                           \
-    } while (0)
-#else
-#define MM_LONG_PICK(TT) MM_LONG_LAUNCH(TT, 2, 1)
-#endif
-        if (dtype == MMCMC_F32)
-            MM_LONG_PICK(float);
-        else
-            MM_LONG_PICK(double);
-#undef MM_LONG_PICK
+#define MM_LONG_LAUNCH(TT)                                                                                          \
+    hipLaunchKernelGGL(mm_chain_fft_long_kernel<TT>, dim3(grid), dim3(64), kStatsLongLds, stream, (const TT *)sample, \
+                       (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, lp.n_wg, tw, wN, \
+                       means, ssq, ws)
+            if (dtype == MMCMC_F32)
+                MM_LONG_LAUNCH(float);
+            else
+                MM_LONG_LAUNCH(double);
 #undef MM_LONG_LAUNCH
         }
-        MM_HIP(le);
         MM_HIP(hipGetLastError());
         const unsigned int total_b = (unsigned int)(dim * lp.N);
         const unsigned int nb_red = (total_b + 63) / 64 * n_parts, nb_wb = wb_part ? (unsigned int)dim * MM_WB_CHUNKS : 0u;

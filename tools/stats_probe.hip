@@ -1,5 +1,6 @@
-// Stand-alone driver of the statistics' half-chain kernel (mm_stats.hip) for A/B timing of its phases:
-//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -std=c++17 [-DMM_STATS_PROBE_SKIP_TILES] [-DMM_STATS_PROBE_SKIP_CENTER] tools/stats_probe.hip -o /tmp/stats_probe
+// Stand-alone driver of the statistics' half-chain kernels (mm_stats.hip) as the library builds them: time by wave count
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -std=c++17 tools/stats_probe.hip mini_mcmc_amd/csrc/mm_tracker.hip -o /tmp/stats_probe
+//   (mm_tracker.hip: the statistics unit calls two of its entry points)
 #include "../mini_mcmc_amd/csrc/mm_stats.hip"
 #include <cstdio>
 #ifndef MM_PROBE_VEC
