@@ -322,7 +322,7 @@ int mmcmc_target_register_source(const char *name, int dim, const char *hip_sour
  * codes (MMCMC_ERR_NO_DEVICE without a GPU) -- and the kind is accepted wherever a user kind is: MH, HMC, NUTS, the device
  * groups, mmcmc_logp_grad_batch, and as the target of mmcmc_proposal_register_source.
  *   Differentiable: + - * / and unary minus in every S / T combination, mm_fma, mm_logT, mm_expT, mm_sqrtT, mm_absT,
- *   mm_maxT, mm_minT; S(c) makes a constant; < > <= >= compare values, so a body may branch on them.  Anything else called
+ *   mm_maxT, mm_minT, mm_softplusT (log(1 + e^a)), mm_sigmoidT; S(c) makes a constant; < > <= >= compare values, so a body may branch on them.  Anything else called
  *   on an S (mm_logf, sinf, ...) has no dual overload: the unit does not compile and the compiler's text arrives in `log`.
  *   Constants and parameters written as T (T(100) * t, P.p[0] * x[0]) cost one multiplication per tangent, the same written
  *   as S (S(100) * t) two operations: prefer T where the body allows it.
@@ -338,6 +338,32 @@ int mmcmc_target_register_source(const char *name, int dim, const char *hip_sour
  *   The value returned next to the gradient equals logp<T> bit for bit, and host and device agree bit for bit
  *   (-ffp-contract=off; every derivative formula has one fixed operation order). */
 int mmcmc_target_register_logp_source(const char *name, int dim, const char *hip_source, int *kind_out, char *log, size_t log_len);
+
+/* A target that carries DATA: the GPU analogue of `struct LogisticRegression { x, y }` implementing `GradientTarget` -- a Rust
+ * struct owns whatever it likes, a run-time compiled functor sees P.p[0..8) and P.mat.  For a kind registered here P.mat is
+ * an array of `data_len` elements of the caller's own, not a dim x dim matrix.  `flavour` says what `hip_source` defines:
+ * MMCMC_SOURCE_LOGP_GRAD mmcmc_user_target<T> (as for mmcmc_target_register_source), MMCMC_SOURCE_LOGP mmcmc_user_logp<T>
+ * (as for mmcmc_target_register_logp_source); csrc/mm_data.h (mm_data_row) and csrc/mm_autodiff.h are included in front of it.
+ *   The length is the KIND's, fixed here.  In every mmcmc_target_desc of this kind `matrix` must point at `data_len` host
+ *   doubles (NULL: MMCMC_ERR_INVALID_ARG from every create and from mmcmc_logp_grad_batch).  mmcmc_mh_create,
+ *   mmcmc_hmc_create, mmcmc_nuts_create, the group constructors (one copy per device), mmcmc_logp_grad_batch and a proposal
+ *   registered over the kind upload that many values, converted once to the element type the functor runs in (f32 for f32
+ *   handles and NUTS modes 0 / 1, f64 otherwise).  The handle owns its device copy: the host array may be freed or
+ *   overwritten as soon as create returns.  Two handles of one kind over different arrays sample different densities; the
+ *   compiled unit is shared.
+ *   `data_len` is a CAPACITY: a model with a run-time number of rows passes it in `params` and reads fewer elements.
+ *   Reading P.mat beyond data_len is the caller's fault, as reading `matrix` beyond dim x dim is for every other kind.
+ *   The row index of mm_data_row must not depend on x, and the bounds of the loop over the rows come from P.p or constants:
+ *   every lane of a wave then reads the same address and the row arrives through the scalar data path.
+ *   Leave the loop over the ROWS rolled and unroll the loops over the coordinates (MM_UNROLL), as above.
+ *   Status codes: those of mmcmc_target_register_source; in addition data_len == 0, an unknown flavour or a data_len whose
+ *   byte count overflows size_t is MMCMC_ERR_INVALID_ARG.  A failed device allocation at create returns the HIP error. */
+#define MMCMC_SOURCE_LOGP_GRAD 0 /* source defines mmcmc_user_target<T> (as mmcmc_target_register_source) */
+#define MMCMC_SOURCE_LOGP 1      /* source defines mmcmc_user_logp<T> (as mmcmc_target_register_logp_source) */
+int mmcmc_target_register_data_source(const char *name, int dim, size_t data_len, int flavour, const char *hip_source, int *kind_out, char *log, size_t log_len);
+/* the data length of `kind`: what mmcmc_target_register_data_source fixed, 0 for a built-in kind and for every kind
+ * registered without data; MMCMC_ERR_INVALID_ARG (and 0) for a kind nobody registered */
+int mmcmc_target_data_len(int kind, size_t *data_len_out);
 
 /* Which compiler builds run-time compiled units (process-wide; default AUTO).  AUTO: `hipcc --genco` in a child process
  * wherever hipcc is found (PATH, then /opt/rocm/bin), hipRTC (libhiprtc.so, bound at run time) otherwise.  A hipRTC was

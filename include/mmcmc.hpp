@@ -498,6 +498,48 @@ inline Target AutodiffTarget(const std::string &name, int dim, const std::string
     return detail::register_target(mmcmc_target_register_logp_source, "mmcmc_target_register_logp_source", name, dim, logp_source, params);
 }
 
+/* ... and over DATA: the kind is registered with data.size() values (mmcmc_target_register_data_source), which the functor
+ * reads as P.mat[0 .. data_len) (csrc/mm_data.h: mm_data_row) and every sampler created from the Target copies to its
+ * device.  with_data(t, other) is the same compiled kind over another array of that size. */
+namespace detail {
+inline Target register_data_target(int flavour, const std::string &name, int dim, const std::string &source,
+                                   const std::vector<double> &params, const std::vector<double> &data)
+{
+    int kind = 0;
+    std::string log(1 << 16, '\0');
+    const int st = mmcmc_target_register_data_source(name.c_str(), dim, data.size(), flavour, source.c_str(), &kind, &log[0], log.size());
+    if (st != MMCMC_OK)
+        throw Error(st, std::string("mmcmc_target_register_data_source: ") + std::string(log.c_str()));
+    Target t;
+    t.d.kind = kind;
+    t.d.dim = dim;
+    for (size_t i = 0; i < params.size() && i < 8; ++i)
+        t.d.params[i] = params[i];
+    t.matrix = data;
+    return t;
+}
+} // namespace detail
+inline Target UserTarget(const std::string &name, int dim, const std::string &hip_source, const std::vector<double> &params,
+                         const std::vector<double> &data)
+{
+    return detail::register_data_target(MMCMC_SOURCE_LOGP_GRAD, name, dim, hip_source, params, data);
+}
+inline Target AutodiffTarget(const std::string &name, int dim, const std::string &logp_source, const std::vector<double> &params,
+                             const std::vector<double> &data)
+{
+    return detail::register_data_target(MMCMC_SOURCE_LOGP, name, dim, logp_source, params, data);
+}
+inline Target with_data(const Target &t, const std::vector<double> &data)
+{
+    size_t len = 0;
+    check(mmcmc_target_data_len(t.d.kind, &len), "mmcmc_target_data_len");
+    if (len == 0 || data.size() != len)
+        throw Error(MMCMC_ERR_INVALID_ARG, "with_data: the kind was registered with another number of values");
+    Target r = t;
+    r.matrix = data;
+    return r;
+}
+
 /* ---- HMC over several GPUs from one call: run() executes every chain (ChainRunner::run, core.rs:176-186) ---- */
 template <class T> class HMCGroup {
     mmcmc_hmc_group *g_ = nullptr;

@@ -174,6 +174,8 @@ SIGNATURES = {
     "mmcmc_draw_noise_mh": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_size_t, C.c_int, C.c_int, _vp, _vp, C.c_int]),
     "mmcmc_target_register_source": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     "mmcmc_target_register_logp_source": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    "mmcmc_target_register_data_source": (C.c_int, [C.c_char_p, C.c_int, C.c_size_t, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    "mmcmc_target_data_len": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "mmcmc_discrete_register_source": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     "mmcmc_proposal_register_source": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     "mmcmc_hmc_group_create": (C.c_int, [C.POINTER(_vp), _TP, _vp, C.c_size_t, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),

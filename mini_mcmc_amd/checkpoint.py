@@ -6,6 +6,10 @@ checkpoint holds exactly these, and a handle restored from one continues bit for
 process, or as a device group with another number of shards (a group's checkpoint has a single handle's layout).  The
 reference marks this as a TODO (nuts.rs:524: "Somehow save state of the chains and enable continuing runs").
 
+A checkpoint stores the target's KIND, not its parameters and not the data of a kind that carries data (`UserTarget(...,
+data=)`): restoring onto a handle created over another array continues from the stored state under the new density, which is
+the caller's business.  Created over the same array, the handle continues bit for bit.
+
 Not in a checkpoint: accept counts (per run), NUTS's cumulative leapfrog counts and depth histogram, tracker state
 (`MultiChainTracker`), the kernel variant and iters_per_launch (none of them changes a result).
 

@@ -126,6 +126,8 @@ int validate_target(const mmcmc_target_desc *t)
             return MMCMC_ERR_UNSUPPORTED; /* an integer-state model belongs to mmcmc_mh_discrete_create */
         if (mm_rtc_is_model(u) && mm_rtc_base_kind(u) == MMCMC_GAUSSIAN_ND && !t->matrix)
             return MMCMC_ERR_INVALID_ARG;
+        if (mm_rtc_data_len(u) && !t->matrix)
+            return MMCMC_ERR_INVALID_ARG; /* a kind that carries data: its functor is never run with P.mat == nullptr */
         break;
     }
     }
@@ -139,7 +141,8 @@ template <class T> int make_params(const mmcmc_target_desc *t, mm_tparams<T> *P,
     /* a model over a BUILT-IN target derives its parameter block like that target (Sigma^-1, 1 / sigma^2, ...) */
     const int base = t->kind >= MM_USER_KIND_BASE ? mm_rtc_base_kind(mm_rtc_find(t->kind)) : t->kind;
     if (t->kind >= MM_USER_KIND_BASE && !(base >= 0 && base < MM_USER_KIND_BASE)) {
-        /* user target: the description's parameters as they are; `matrix`, if given, is dim x dim */
+        /* user target: the description's parameters as they are; `matrix`, if given, is dim x dim -- or, for a kind registered
+         * with its data (mmcmc_target_register_data_source), that kind's data_len */
         std::memset(P, 0, sizeof *P);
         for (int i = 0; i < 8; ++i)
             P->p[i] = (T)t->params[i];
@@ -147,6 +150,9 @@ template <class T> int make_params(const mmcmc_target_desc *t, mm_tparams<T> *P,
         return MMCMC_ERR_INVALID_ARG;
     if (t->kind == MMCMC_GAUSSIAN_ND || (t->kind >= MM_USER_KIND_BASE && t->matrix)) {
         size_t n = (size_t)t->dim * t->dim;
+        if (t->kind >= MM_USER_KIND_BASE)
+            if (const size_t data_len = mm_rtc_data_len(mm_rtc_find(t->kind)))
+                n = data_len;
         std::vector<T> h(n);
         for (size_t i = 0; i < n; ++i)
             h[i] = (T)t->matrix[i];

@@ -15,7 +15,7 @@
  * the gradient.  mm_ad_logp_grad seeds unit tangents and runs ceil(dim / W) passes, W = min(dim, MM_AD_MAX_W).
  *
  * Differentiable operations (every dual / scalar combination): + - * /, unary minus, mm_fma, mm_logT, mm_expT, mm_sqrtT,
- * mm_absT, mm_maxT, mm_minT; < > <= >= compare the values.  An operation without a dual overload does not compile.
+ * mm_absT, mm_maxT, mm_minT, mm_softplusT, mm_sigmoidT; < > <= >= compare the values.  An operation without a dual overload does not compile.
  * mm_absT / mm_maxT / mm_minT are differentiated one-sidedly at the kink: d|x| at 0 is +dx, a tie takes the SECOND
  * argument's tangents.  The tangents of mm_sqrtT(a) and mm_logT(a) divide by sqrt(a) and a: inf / NaN at a = 0.  A body's loops
  * over the coordinates must carry MM_UNROLL (see "Registers").
@@ -46,6 +46,24 @@ MM_HD float mm_absT(float x) { return fabsf(x); }
 MM_HD double mm_absT(double x) { return fabs(x); }
 MM_HD float mm_maxT(float a, float b) { return fmaxf(a, b); }
 MM_HD double mm_maxT(double a, double b) { return fmax(a, b); }
+
+/* softplus(a) = log(1 + e^a) and sigmoid(a) = 1 / (1 + e^-a), what every GLM's likelihood is made of, without overflow at
+ * either end: with e = exp(-|a|) <= 1 and q = 1 + e,
+ *     softplus = max(a, 0) + log(q)        sigmoid = a >= 0 ? 1 / q : e / q        (sigmoid(-a) = the other branch)
+ * in this order.  They are primitives because the composition max(a, 0) + log(1 + exp(-|a|)) of the operations below is
+ * differentiated wrongly at a = 0: the tie of mm_maxT takes the constant's tangent (0) and mm_absT at 0 takes +a', which
+ * leaves -a' / 2 where the derivative is +a' / 2 -- at the very point a chain started at 0 sits. */
+template <class T> MM_HD T mm_softplusT(T a)
+{
+    const T e = mm_expT(-mm_absT(a));
+    return mm_maxT(a, T(0)) + mm_logT(T(1) + e);
+}
+template <class T> MM_HD T mm_sigmoidT(T a)
+{
+    const T e = mm_expT(-mm_absT(a)), q = T(1) + e;
+    const T hi = T(1) / q, lo = e / q;
+    return a >= T(0) ? hi : lo;
+}
 
 #define MM_AD_FOR MM_UNROLL for (int k = 0; k < W; ++k)
 
@@ -250,6 +268,29 @@ template <class T, int W> struct mm_dual {
         mm_dual r;
         r.v = mm_sqrtT(a.v);
         MM_AD_FOR r.d[k] = (T(0.5) * a.d[k]) / r.v;
+        return r;
+    }
+
+    /* ---- softplus' = a' * sigmoid(a) (1, on top of sigmoid's own: exp, 1 + e and the quotient), sharing e and q with the value;
+     *      sigmoid' = a' * (hi * lo) (2), hi = 1 / q and lo = e / q, one of which is the value: s (1 - s) = e / q^2 */
+    friend MM_HD mm_dual mm_softplusT(const mm_dual &a)
+    {
+        mm_dual r;
+        const T e = mm_expT(-mm_absT(a.v)), q = T(1) + e;
+        r.v = mm_maxT(a.v, T(0)) + mm_logT(q);
+        const T hi = T(1) / q, lo = e / q;
+        const T s = a.v >= T(0) ? hi : lo;
+        MM_AD_FOR r.d[k] = a.d[k] * s;
+        return r;
+    }
+    friend MM_HD mm_dual mm_sigmoidT(const mm_dual &a)
+    {
+        mm_dual r;
+        const T e = mm_expT(-mm_absT(a.v)), q = T(1) + e;
+        const T hi = T(1) / q, lo = e / q;
+        r.v = a.v >= T(0) ? hi : lo;
+        const T w = hi * lo;
+        MM_AD_FOR r.d[k] = a.d[k] * w;
         return r;
     }
 

@@ -184,6 +184,8 @@ template <class TT, class ST> struct Nuts : NutsBase {
                                                  the library built for itself is not a kind a caller may name */
             if (mm_rtc_dim(user) != t->dim)
                 return MMCMC_ERR_SHAPE;
+            if (!builtin_user && mm_rtc_data_len(user) && !t->matrix)
+                return MMCMC_ERR_INVALID_ARG; /* a kind that carries data: its functor is never run with P.mat == nullptr */
             if (!builtin_user) {
                 DevGuard gu(device);
                 if (!mm_rtc_nuts_usable(user, create_mode))
@@ -214,7 +216,8 @@ template <class TT, class ST> struct Nuts : NutsBase {
         DevGuard g(device);
         const size_t cd = n_chains * (size_t)dim;
         if (t->kind == MMCMC_GAUSSIAN_ND || (user && t->matrix)) {
-            std::vector<TT> h((size_t)dim * dim);
+            const size_t data_len = user && !builtin_user ? mm_rtc_data_len(user) : 0; /* a data kind: its own length */
+            std::vector<TT> h(data_len ? data_len : (size_t)dim * dim);
             for (size_t i = 0; i < h.size(); ++i)
                 h[i] = (TT)t->matrix[i];
             MM_HIP(hipMalloc((void **)&d_mat, h.size() * sizeof(TT)));

@@ -13,6 +13,9 @@ int mm_rtc_dim(const mm_user_target *t);
  * (a built-in kind, or a user kind); -1 for a plain user target */
 int mm_rtc_base_kind(const mm_user_target *t);
 int mm_rtc_is_model(const mm_user_target *t);
+/* a kind registered with mmcmc_target_register_data_source (or a model over one): the number of doubles the description's
+ * `matrix` holds, which every create path uploads instead of dim x dim; 0 for every other kind */
+size_t mm_rtc_data_len(const mm_user_target *t);
 /* an integer-state model (mmcmc_discrete_register_source); `args` = mm_discrete_user_args, one wave per workgroup */
 int mm_rtc_is_discrete(const mm_user_target *t);
 /* a unit the library built for itself (mm_rtc_builtin / mm_rtc_builtin_nuts): not a kind a caller may pass in a description */

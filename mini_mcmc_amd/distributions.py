@@ -153,22 +153,60 @@ class UserTarget(Target):
     `source` is HIP C++ defining `template <class T> struct mmcmc_user_target` with `static constexpr int dim`,
     `logp(P, x)` and `logp_grad(P, x, g)` (include/mmcmc.h: mmcmc_target_register_source); it is compiled at run time
     (`hipcc --genco` in a child process where hipcc is installed, else hipRTC) into the engine's MH / HMC kernels for f32 and f64 and its NUTS kernel for the three type modes.  `params` (up to 8 numbers) arrive as `P.p[i]`,
-    `matrix` ([dim, dim]) as `P.mat`.  `UserTarget.compile_log` holds the compiler's diagnostics."""
+    `matrix` ([dim, dim]) as `P.mat`.  `UserTarget.compile_log` holds the compiler's diagnostics.
+
+    `data=` (any array, flattened to float64) binds a dataset instead of a matrix: the kind is registered with
+    `data_len = data.size` (mmcmc_target_register_data_source), the functor reads `P.mat[0 .. data_len)` -- `mm_data_row`
+    of csrc/mm_data.h reads one row -- and every sampler created over the target uploads its own copy.  `with_data(other)`
+    gives the same compiled kind over another array of that size.  A model with fewer rows than the capacity passes the count
+    in `params`."""
 
     _register = "mmcmc_target_register_source"
+    _flavour = 0  # MMCMC_SOURCE_LOGP_GRAD
 
-    def __init__(self, name: str, dim: int, source: str, params=(), matrix=None):
+    def __init__(self, name: str, dim: int, source: str, params=(), matrix=None, data=None):
+        if matrix is not None and data is not None:
+            raise ValueError("matrix= and data= share P.mat: give one of them")
+        if data is not None:
+            matrix = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
         super().__init__(dim, params, matrix)
+        #: number of doubles the kind was registered with (mmcmc_target_register_data_source), 0 for a kind without data
+        self.data_len = 0 if data is None else int(self._matrix.size)
         kind = C.c_int(0)
         log = C.create_string_buffer(1 << 16)
-        st = getattr(L.lib(), self._register)(name.encode(), int(dim), source.encode(), C.byref(kind), log, len(log))
+        if data is None:
+            register = self._register
+            st = getattr(L.lib(), register)(name.encode(), int(dim), source.encode(), C.byref(kind), log, len(log))
+        else:
+            register = "mmcmc_target_register_data_source"
+            st = L.lib().mmcmc_target_register_data_source(name.encode(), int(dim), self.data_len, self._flavour, source.encode(),
+                                                           C.byref(kind), log, len(log))
         self.compile_log = log.value.decode(errors="replace")
         if st != L.OK:
-            raise L.MmcmcError(st, self._register + (": " + self.compile_log[-2000:] if self.compile_log else ""))
+            raise L.MmcmcError(st, register + (": " + self.compile_log[-2000:] if self.compile_log else ""))
         self.kind = kind.value
         self.name = name
         #: "hipcc" (`hipcc --genco` in a child process: the default wherever hipcc is installed) or "hiprtc"
         self.compiler = {1: "hipcc", 2: "hiprtc"}.get(L.lib().mmcmc_rtc_unit_compiler(self.kind), "?")
+
+    def with_data(self, new_data) -> "UserTarget":
+        """A target of the SAME kind over another array of the same size: nothing is compiled, the kind is the compiled unit
+        and the array travels in the description a sampler is created with (which copies it to the device)."""
+        if not self.data_len:
+            raise ValueError("with_data needs a target registered with data=")
+        new = np.ascontiguousarray(new_data, dtype=np.float64).reshape(-1)  # like data=: not copied here, a sampler's create copies it
+        if new.size != self.data_len:
+            raise ValueError(f"this kind was registered with {self.data_len} values, got {new.size}")
+        other = object.__new__(type(self))
+        other.__dict__.update(self.__dict__)
+        other.params = list(self.params)
+        other._matrix = new
+        return other
+
+    @property
+    def data(self):
+        """the bound array (flattened float64), or None for a target without data"""
+        return self._matrix if self.data_len else None
 
 
 class AutodiffTarget(UserTarget):
@@ -179,16 +217,18 @@ class AutodiffTarget(UserTarget):
     `template <class S> MM_HD static S logp(const mm_tparams<T> &P, const S *x)`, written once over the scalar type `S`
     (include/mmcmc.h: mmcmc_target_register_logp_source lists the differentiable operations).  The gradient HMC and NUTS
     need is forward-mode automatic differentiation of that body on the device (csrc/mm_autodiff.h); everything else is
-    `UserTarget`'s.
+    `UserTarget`'s, `data=` and `with_data` included.
 
     Put `MM_UNROLL` in front of every loop over the coordinates: a loop left rolled indexes the array of dual numbers at run
-    time, which moves it from registers to scratch memory (at dim 32: 1168 B per lane in f32, 2592 B in f64).  The tangents
+    time, which moves it from registers to scratch memory (at dim 32: 1168 B per lane in f32, 2592 B in f64).  The loop over
+    the ROWS of a bound array stays rolled.  The tangents
     of `mm_sqrtT(a)` and `mm_logT(a)` divide by sqrt(a) and a: inf / NaN at a = 0, like the derivatives themselves."""
 
     _register = "mmcmc_target_register_logp_source"
+    _flavour = 1  # MMCMC_SOURCE_LOGP
 
-    def __init__(self, name: str, dim: int, logp_source: str, params=(), matrix=None):
-        super().__init__(name, dim, logp_source, params, matrix)
+    def __init__(self, name: str, dim: int, logp_source: str, params=(), matrix=None, data=None):
+        super().__init__(name, dim, logp_source, params, matrix, data)
 
 
 RTC_COMPILERS = {"auto": 0, "hipcc": 1, "hiprtc": 2}

@@ -85,8 +85,24 @@ pub enum GpuTarget {
     RosenbrockND,
     /// zero-mean Gaussian with a dense precision matrix, row-major `[dim, dim]` (not in the reference)
     GaussianND { precision: Vec<f64> },
+    /// a kind registered with `register_target_data_source` over its dataset: the GPU analogue of
+    /// `struct LogisticRegression { x, y }` implementing `GradientTarget` (see `GpuTarget::with_data`)
+    UserData { kind: i32, params: [f64; 8], data: Vec<f64> },
 }
 impl GpuTarget {
+    /// A target of a kind that carries data (`register_target_data_source`), over `data`: exactly the `data_len` values the
+    /// kind was registered with (`mmcmc_target_data_len`).  The same kind over another array is another density; nothing is
+    /// recompiled.  Every sampler created from it copies the array to its device.
+    pub fn with_data(kind: i32, params: &[f64], data: Vec<f64>) -> Result<Self, MmcmcError> {
+        let mut len: usize = 0;
+        check(unsafe { sys::mmcmc_target_data_len(kind, &mut len) })?;
+        if len == 0 || len != data.len() || params.len() > 8 {
+            return Err(MmcmcError { status: sys::MMCMC_ERR_INVALID_ARG, message: format!("the kind carries {} values, got {}", len, data.len()) });
+        }
+        let mut p = [0.0; 8];
+        p[..params.len()].copy_from_slice(params);
+        Ok(GpuTarget::UserData { kind, params: p, data })
+    }
     fn desc(&self, dim: usize) -> sys::mmcmc_target_desc {
         let mut d = sys::mmcmc_target_desc { kind: 0, dim: dim as i32, params: [0.0; 8], matrix: null() };
         match self {
@@ -107,6 +123,11 @@ impl GpuTarget {
             GpuTarget::GaussianND { precision } => {
                 d.kind = sys::MMCMC_GAUSSIAN_ND;
                 d.matrix = precision.as_ptr(); // copied to the device by *_create
+            }
+            GpuTarget::UserData { kind, params, data } => {
+                d.kind = *kind;
+                d.params = *params;
+                d.matrix = data.as_ptr(); // data_len values, copied to the device by *_create
             }
         }
         d
@@ -617,6 +638,16 @@ pub fn register_target_source(name: &str, dim: usize, hip_source: &str) -> Resul
 /// The same from the log-density alone (`mmcmc_target_register_logp_source`): the gradient is forward-mode autodiff on the device.
 pub fn register_target_logp_source(name: &str, dim: usize, logp_source: &str) -> Result<i32, String> {
     register_target_with(sys::mmcmc_target_register_logp_source, name, dim, logp_source)
+}
+/// Either of the two for a kind that carries data (`mmcmc_target_register_data_source`): `logp_only` says whether `source`
+/// defines `mmcmc_user_logp<T>` (autodiff) or `mmcmc_user_target<T>`; the functor reads `P.mat[0 .. data_len)`.
+pub fn register_target_data_source(name: &str, dim: usize, data_len: usize, logp_only: bool, source: &str) -> Result<i32, String> {
+    let (n, s) = (std::ffi::CString::new(name).unwrap(), std::ffi::CString::new(source).unwrap());
+    let mut kind: c_int = 0;
+    let mut log = vec![0 as std::os::raw::c_char; 1 << 16];
+    let flavour = if logp_only { sys::MMCMC_SOURCE_LOGP } else { sys::MMCMC_SOURCE_LOGP_GRAD };
+    let st = unsafe { sys::mmcmc_target_register_data_source(n.as_ptr(), dim as c_int, data_len, flavour, s.as_ptr(), &mut kind, log.as_mut_ptr(), log.len()) };
+    if st == sys::MMCMC_OK { Ok(kind) } else { Err(unsafe { CStr::from_ptr(log.as_ptr()) }.to_string_lossy().into_owned()) }
 }
 type RegisterTargetFn = unsafe extern "C" fn(*const std::os::raw::c_char, c_int, *const std::os::raw::c_char, *mut c_int, *mut std::os::raw::c_char, usize) -> c_int;
 fn register_target_with(register: RegisterTargetFn, name: &str, dim: usize, source: &str) -> Result<i32, String> {

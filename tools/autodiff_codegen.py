@@ -22,7 +22,7 @@ BODY = os.path.join(ROOT, "tests", "cpp", "autodiff_cases", "rosenbrock.inc")
 
 KERNEL = r"""
 #include <hip/hip_runtime.h>
-#include "mm_autodiff.h"
+#include "%(header)s"
 %(body)s
 template <class T> __device__ __forceinline__ void batch(const mm_tparams<T> &P, const T *x, T *logp, T *grad, unsigned long long n)
 {
@@ -37,7 +37,7 @@ extern "C" __global__ void ad_logp_grad_f32(const mm_tparams<float> P, const flo
 extern "C" __global__ void ad_logp_grad_f64(const mm_tparams<double> P, const double *x, double *logp, double *grad, unsigned long long n) { batch<double>(P, x, logp, grad, n); }
 """
 
-FIELDS = (".private_segment_fixed_size", ".vgpr_count", ".sgpr_count", ".vgpr_spill_count")
+FIELDS = (".private_segment_fixed_size", ".vgpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count")
 
 
 def tools():
@@ -46,13 +46,14 @@ def tools():
     return (hipcc, readelf) if os.path.exists(hipcc) and os.path.exists(readelf) else None
 
 
-def kernel_metadata(dim: int) -> dict:
-    """{kernel name: {field: int}} for the batch kernels at `dim`."""
+def kernel_metadata(dim: int, body: str = BODY, header: str = "mm_autodiff.h") -> dict:
+    """{kernel name: {field: int}} for the batch kernels at `dim` around the log-density in the file `body` (default: RosenbrockND;
+    a body that reads a bound array needs header="mm_data.h": tests/test_data_target_codegen.py)."""
     hipcc, readelf = tools()
     with tempfile.TemporaryDirectory() as d:
         src, out = os.path.join(d, "unit.hip"), os.path.join(d, "unit.hsaco")
         with open(src, "w") as f:
-            f.write(KERNEL % {"body": open(BODY).read()})
+            f.write(KERNEL % {"body": open(body).read(), "header": header})
         subprocess.run([hipcc, "--genco", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", f"-DMM_USER_DIM={dim}",
                         "-Wno-pass-failed", "-I" + CSRC, "-o", out, src], check=True, capture_output=True, text=True)
         notes = ""
