@@ -43,7 +43,8 @@ extern "C" {
  *   mmcmc_{mh,hmc,nuts}_group_stream_position, mmcmc_{mh,hmc,nuts}_group_set_iteration, mmcmc_{mh,hmc,nuts}_group_params,
  *   mmcmc_hmc_group_set_step_size, mmcmc_hmc_group_set_n_leapfrog, mmcmc_mh_group_set_proposal_std,
  *   mmcmc_nuts_group_adapt_state, mmcmc_nuts_group_set_adapt_state, mmcmc_nuts_group_set_target_accept_p;
- *   rank-normalised diagnostics: mmcmc_rank_normalize, mmcmc_quantiles, mmcmc_rank_diagnostics.
+ *   rank-normalised diagnostics: mmcmc_rank_normalize, mmcmc_quantiles, mmcmc_rank_diagnostics;
+ *   mmcmc_group_bind_collectives.
  * A binding checks mmcmc_version() >= the version it was generated from (rust/mini-mcmc-hip: assert_abi, in every constructor). */
 #define MMCMC_VERSION 102 /* 0.1.2 */
 
@@ -436,6 +437,14 @@ int mmcmc_proposal_register_source(const char *name, int target_kind, int dim, c
  *   and writes each shard's elapsed device milliseconds into ms [n_devices].
  *   _exchange: how the diagnostics' statistics will travel -- decided in _create, where the RCCL communicators are made
  *   (ncclCommInitAll; *status as *used_rccl above, *n_rccl_ranks = ranks of the communicator or 0). */
+/* The collectives are bound ONCE per process: by the first group that is created (librccl, found by the loader), or before
+ * that by this call from the library at `library_path` -- dlopen(RTLD_NOW | RTLD_LOCAL) and dlsym ON THAT HANDLE for
+ * ncclCommInitAll, ncclCommDestroy, ncclAllGather, ncclAllReduce, so the named library's functions are taken even where
+ * another librccl is already mapped.  MMCMC_ERR_INVALID_ARG: library_path is NULL, the library cannot be loaded, one of the
+ * four symbols is missing, or the collectives are already bound (by this call or by an earlier group creation).
+ * ranks_may_share_a_device != 0: a device listed twice no longer sends the statistics through the host (*used_rccl 1, not
+ * 0).  Bind that way ONLY a library that accepts several ranks on one device; RCCL itself refuses them. */
+int mmcmc_group_bind_collectives(const char *library_path, int ranks_may_share_a_device);
 typedef struct mmcmc_hmc_group mmcmc_hmc_group;
 int mmcmc_hmc_group_create(mmcmc_hmc_group **out, const mmcmc_target_desc *target, const void *init, size_t n_chains,
                            double step_size, int n_leapfrog, int dtype, const int *devices, int n_devices);
@@ -497,7 +506,8 @@ int mmcmc_split_rhat_mean_ess(const void *sample, int sample_is_device, int dtyp
  * partials: device-side sufficient statistics of the LOCAL chains -- means, ssq: device [2*n_chains, dim] in splitcat
  * order (first halves of all local chains, then second halves), acov_sum: device [n/2, dim] un-normalised lag sums
  * over the local half-chains.  All-gather the first two, all-reduce(sum) the third, then
- * finish (host): the arithmetic of stats.rs:449-465, :425-427, :509-545 on the global statistics. */
+ * finish (host): the arithmetic of stats.rs:449-465, :425-427, :509-545 on the global statistics (f32; the cross-chain
+ * sums in f64 as on the device, so the result does not drift from the single-GPU one as the chain count grows). */
 int mmcmc_stats_partials(const void *sample, int dtype, size_t n_chains, size_t n, size_t dim, float *means,
                          float *ssq, float *acov_sum, int device, void *stream);
 int mmcmc_stats_finish(const float *means, const float *ssq, const float *acov_sum, size_t n_half_chains, size_t m,

@@ -540,6 +540,13 @@ inline Target with_data(const Target &t, const std::vector<double> &data)
     return r;
 }
 
+/* the groups' collectives from a named library instead of librccl (mmcmc_group_bind_collectives): once per process, before
+ * the first group; ranks_may_share_a_device only for a library that accepts several ranks on one device */
+inline void bind_collectives(const std::string &library_path, bool ranks_may_share_a_device = false)
+{
+    check(mmcmc_group_bind_collectives(library_path.c_str(), ranks_may_share_a_device ? 1 : 0), "mmcmc_group_bind_collectives");
+}
+
 /* ---- HMC over several GPUs from one call: run() executes every chain (ChainRunner::run, core.rs:176-186) ---- */
 template <class T> class HMCGroup {
     mmcmc_hmc_group *g_ = nullptr;

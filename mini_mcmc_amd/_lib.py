@@ -178,6 +178,7 @@ SIGNATURES = {
     "mmcmc_target_data_len": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "mmcmc_discrete_register_source": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     "mmcmc_proposal_register_source": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    "mmcmc_group_bind_collectives": (C.c_int, [C.c_char_p, C.c_int]),
     "mmcmc_hmc_group_create": (C.c_int, [C.POINTER(_vp), _TP, _vp, C.c_size_t, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "mmcmc_hmc_group_seed": (C.c_int, [_vp, C.c_uint64]),
     "mmcmc_hmc_group_set_chain_offset": (C.c_int, [_vp, C.c_uint64]),

@@ -17,7 +17,9 @@
  * all-reduces the lag sums (ncclAllReduce), and the host finish (mmcmc_stats_finish) runs on the gathered statistics
  * in the single-GPU order.  RCCL is loaded at run time (librccl.so.1: the copy PyTorch has already mapped, if any);
  * without it, or when a device appears twice in the list (several shards on one GPU: what a one-GPU test box can
- * exercise), the few KB of statistics are exchanged through the host instead.
+ * exercise), the few KB of statistics are exchanged through the host instead.  mmcmc_group_bind_collectives binds the four
+ * collective entry points from a library the caller names instead, before the first group exists; bound as accepting several
+ * ranks on one device, a device listed twice keeps the collective branch (tests/c/fake_collectives.c: N > 1 ranks on one GPU).
  */
 #include "../../include/mmcmc.h"
 #include "mm_hostcopy.h"
@@ -39,7 +41,8 @@
 
 namespace {
 
-/* ---- RCCL, bound at run time ---- */
+/* ---- the collectives (RCCL), bound at run time: once per process, by the first group that asks or -- before that -- by
+ * mmcmc_group_bind_collectives from a library the caller names ---- */
 typedef void *ncclComm_t;
 struct Rccl {
     void *lib = nullptr;
@@ -48,27 +51,77 @@ struct Rccl {
     int (*AllGather)(const void *, void *, size_t, int, ncclComm_t, hipStream_t) = nullptr;
     int (*AllReduce)(const void *, void *, size_t, int, int, ncclComm_t, hipStream_t) = nullptr;
     bool ok() const { return CommInitAll && CommDestroy && AllGather && AllReduce; }
+    /* the four entry points of an open library, by dlsym on THAT handle (not the process's first definition) */
+    void take(void *handle)
+    {
+        lib = handle;
+        CommInitAll = (int (*)(ncclComm_t *, int, const int *))dlsym(handle, "ncclCommInitAll");
+        CommDestroy = (int (*)(ncclComm_t))dlsym(handle, "ncclCommDestroy");
+        AllGather = (int (*)(const void *, void *, size_t, int, ncclComm_t, hipStream_t))dlsym(handle, "ncclAllGather");
+        AllReduce = (int (*)(const void *, void *, size_t, int, int, ncclComm_t, hipStream_t))dlsym(handle, "ncclAllReduce");
+    }
 };
 constexpr int kNcclFloat32 = 7, kNcclSum = 0;
 
+struct Binding {
+    std::mutex mu;
+    bool bound = false;       /* decided for the life of the process (also when no library was found) */
+    bool share_device = false; /* the bound library takes several ranks on one device */
+    Rccl r;
+};
+Binding &binding()
+{
+    static Binding b;
+    return b;
+}
+
 Rccl &rccl()
 {
-    static Rccl r;
-    static std::once_flag once;
-    std::call_once(once, [] {
+    Binding &b = binding();
+    std::lock_guard<std::mutex> l(b.mu);
+    if (!b.bound) {
+        b.bound = true;
+        void *lib = nullptr;
         for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            r.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (r.lib)
+            lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
+            if (lib)
                 break;
         }
-        if (!r.lib)
-            return;
-        r.CommInitAll = (int (*)(ncclComm_t *, int, const int *))dlsym(r.lib, "ncclCommInitAll");
-        r.CommDestroy = (int (*)(ncclComm_t))dlsym(r.lib, "ncclCommDestroy");
-        r.AllGather = (int (*)(const void *, void *, size_t, int, ncclComm_t, hipStream_t))dlsym(r.lib, "ncclAllGather");
-        r.AllReduce = (int (*)(const void *, void *, size_t, int, int, ncclComm_t, hipStream_t))dlsym(r.lib, "ncclAllReduce");
-    });
-    return r;
+        if (lib)
+            b.r.take(lib);
+    }
+    return b.r; /* never changes once bound */
+}
+
+/* a device listed twice keeps the collectives only under a library bound as accepting that (RCCL does not) */
+bool collectives_share_devices()
+{
+    Binding &b = binding();
+    std::lock_guard<std::mutex> l(b.mu);
+    return b.bound && b.share_device;
+}
+
+int bind_collectives(const char *library_path, int share_device)
+{
+    if (!library_path)
+        return MMCMC_ERR_INVALID_ARG;
+    Binding &b = binding();
+    std::lock_guard<std::mutex> l(b.mu);
+    if (b.bound)
+        return MMCMC_ERR_INVALID_ARG;
+    void *lib = dlopen(library_path, RTLD_NOW | RTLD_LOCAL);
+    if (!lib)
+        return MMCMC_ERR_INVALID_ARG;
+    Rccl r;
+    r.take(lib);
+    if (!r.ok()) {
+        dlclose(lib);
+        return MMCMC_ERR_INVALID_ARG;
+    }
+    b.r = r;
+    b.share_device = share_device != 0;
+    b.bound = true;
+    return MMCMC_OK;
 }
 
 /* withinvar's cross-chain sums (stats.rs:449-465) over the GATHERED per-half-chain statistics, on the device (round 5: the
@@ -78,7 +131,7 @@ Rccl &rccl()
  * sums of a parameter in index order and forms sum((mean - overall)^2) = Sq - Sd^2 / c2.  gathered: [N][means (part) | ssq (part)],
  * a rank's valid entries first (2 n_i D), zero padding behind. */
 struct GroupCounts {
-    unsigned int n2[64]; /* 2 n_i */
+    unsigned int n2[64]; /* 2 n_i; 64 entries suffice: group_create refuses more than 64 devices, so a group never has more ranks */
 };
 __global__ __launch_bounds__(256) void mm_group_cross_sums_kernel(const float *__restrict__ gathered, size_t part, unsigned int D,
                                                                   float nf, GroupCounts cnt, double *__restrict__ out)
@@ -287,7 +340,7 @@ int group_create(Group **out, int sampler, const mmcmc_target_desc *target, cons
     g->dtype = dtype;
     g->dim = target->dim;
     g->n_chains = n_chains;
-    g->use_rccl = !dup && rccl().ok();
+    g->use_rccl = (!dup || collectives_share_devices()) && rccl().ok();
     g->exchange_status = g->use_rccl ? 1 : dup ? 0 : -1;
     g->sh.resize((size_t)n_devices);
     const size_t esz = g->esize(), base = n_chains / (size_t)n_devices, rem = n_chains % (size_t)n_devices;
@@ -677,7 +730,7 @@ int group_split_rhat_ess(Group *g, float *rhat, float *ess, int *used_rccl)
                 return (int)hipErrorUnknown;
             if (rccl().AllReduce(acov, acov_all, m * D, kNcclFloat32, kNcclSum, s.comm, s.stream) != 0)
                 return (int)hipErrorUnknown;
-            if (i == 0 && N <= 64) { /* the cross-chain sums of ALL ranks' half-chains, from shard 0's copy of the gathered statistics */
+            if (i == 0) { /* the cross-chain sums of ALL ranks' half-chains, from shard 0's copy of the gathered statistics */
                 GroupCounts cnt;
                 for (size_t r = 0; r < N; ++r)
                     cnt.n2[r] = (unsigned int)(2 * g->sh[r].n);
@@ -701,7 +754,7 @@ int group_split_rhat_ess(Group *g, float *rhat, float *ess, int *used_rccl)
      * the device.  Host-exchange path (a device listed twice, no RCCL): the host walks the statistics in splitcat order (first
      * halves of all chains, then second halves) */
     std::vector<float> acov;
-    if (g->use_rccl && N <= 64) {
+    if (g->use_rccl) {
         /* a few KB come back: the reduced lag sums and the N x 4 partial cross-chain sums per parameter */
         Shard &s0 = g->sh[0];
         (void)hipSetDevice(s0.device);
@@ -733,22 +786,11 @@ int group_split_rhat_ess(Group *g, float *rhat, float *ess, int *used_rccl)
     }
     std::vector<float> g_all(N * 2 * part);
     acov.assign(m * D, 0.f);
-    if (g->use_rccl) {
-        Shard &s0 = g->sh[0];
-        (void)hipSetDevice(s0.device);
-        const float *gathered = s0.d_stats + own, *acov_all = gathered + N * 2 * part;
-        hipError_t e = hipMemcpy(g_all.data(), gathered, g_all.size() * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess)
-            e = hipMemcpy(acov.data(), acov_all, acov.size() * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            return (int)e;
-    } else {
-        for (size_t i = 0; i < N; ++i) {
-            std::memcpy(g_all.data() + i * 2 * part, h_own.data() + i * own, 2 * part * sizeof(float));
-            const float *a = h_own.data() + i * own + 2 * part;
-            for (size_t k = 0; k < m * D; ++k)
-                acov[k] += a[k];
-        }
+    for (size_t i = 0; i < N; ++i) {
+        std::memcpy(g_all.data() + i * 2 * part, h_own.data() + i * own, 2 * part * sizeof(float));
+        const float *a = h_own.data() + i * own + 2 * part;
+        for (size_t k = 0; k < m * D; ++k)
+            acov[k] += a[k];
     }
     const size_t C = g->n_chains;
     std::vector<float> means(2 * C * D), ssq(2 * C * D);
@@ -785,6 +827,11 @@ struct mmcmc_nuts_group {
 };
 
 extern "C" {
+
+int mmcmc_group_bind_collectives(const char *library_path, int ranks_may_share_a_device)
+{
+    return bind_collectives(library_path, ranks_may_share_a_device);
+}
 
 int mmcmc_hmc_group_create(mmcmc_hmc_group **out, const mmcmc_target_desc *target, const void *init, size_t n_chains,
                            double step_size, int n_leapfrog, int dtype, const int *devices, int n_devices)

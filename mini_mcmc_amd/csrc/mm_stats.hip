@@ -2379,7 +2379,8 @@ int mmcmc_stats_partials(const void *sample, int dtype, size_t n_chains, size_t 
     return MMCMC_OK;
 }
 
-/* stats.rs:449-465 (withinvar), :425-427 (rhat), :509-545 (ess) on the gathered sufficient statistics, f32.
+/* stats.rs:449-465 (withinvar), :425-427 (rhat), :509-545 (ess) on the gathered sufficient statistics: f32, the
+ * cross-chain sums in f64 (mmcmc_stats_finish).
  * means, ssq: [c2, dim] in splitcat order (first halves of all chains, then second halves); acov_sum [m, dim]. */
 /* from the cross-chain sums to R-hat and ESS of parameter d (stats.rs:459-465, 425-427, 509-545), f32 */
 static float stats_ess_one(float w, float v, const float *acov_sum, size_t c2, size_t m, size_t dim, size_t d,
@@ -2425,24 +2426,26 @@ int mmcmc_stats_finish(const float *means, const float *ssq, const float *acov_s
 {
     if (!means || !ssq || !acov_sum || !rhat || !ess || c2 < 2 || m < 1 || dim == 0)
         return MMCMC_ERR_INVALID_ARG;
-    const float nf = (float)m, cf = (float)c2;
+    const float nf = (float)m;
     std::vector<float> rho(m);
-    /* every parameter's sums run over the half-chains in index order, as before; the loops are nested chain-outer so that the
-     * [c2, dim] arrays are walked once, contiguously (a device group's finish over 131 072 half-chains: 0.4 -> 0.1 ms) */
-    std::vector<float> msum(dim, 0.f), overall(dim), dsum(dim, 0.f), wsum(dim, 0.f);
-    for (size_t c = 0; c < c2; ++c)
-        for (size_t d = 0; d < dim; ++d)
-            msum[d] += means[c * dim + d];
-    for (size_t d = 0; d < dim; ++d)
-        overall[d] = msum[d] / cf;
+    /* The cross-chain sums as the device forms them (mm_stats_tail_kernel): f64 totals of the f32 terms, the means taken
+     * relative to the first half-chain's -- sum((mean - overall)^2) = Sq - Sd^2 / c2.  f32 running totals lose their
+     * digits as the count grows: against float64 they put R-hat off by 1e-7 at 2000 half-chains, 1.5e-5 at 131 072 and
+     * 2.4e-4 at 1 048 576 (a device group's host exchange at 8 x 65 536 chains); these totals hold 5e-8 at every count, and
+     * the host exchange agrees with the single-GPU entry point.  Every parameter's sums run over the half-chains in index order, chain-outer: the [c2, dim] arrays are
+     * walked once, contiguously. */
+    std::vector<double> sd(dim, 0.0), sq(dim, 0.0), ws(dim, 0.0);
     for (size_t c = 0; c < c2; ++c)
         for (size_t d = 0; d < dim; ++d) {
-            const float df = means[c * dim + d] - overall[d];
-            dsum[d] += df * df;
-            wsum[d] += ssq[c * dim + d] / nf; /* biased per-chain variance (quirk Q8) */
+            const double df = (double)(means[c * dim + d] - means[d]);
+            sd[d] += df;
+            sq[d] += df * df;
+            ws[d] += (double)(ssq[c * dim + d] / nf); /* biased per-chain variance (quirk Q8) */
         }
-    for (size_t d = 0; d < dim; ++d)
-        stats_finish_one(dsum[d], wsum[d], acov_sum, c2, m, dim, d, rho, rhat, ess);
+    for (size_t d = 0; d < dim; ++d) {
+        const double dsum = sq[d] - sd[d] * sd[d] / (double)c2; /* sum of (mean - overall mean)^2 */
+        stats_finish_one((float)(dsum > 0.0 ? dsum : 0.0), (float)ws[d], acov_sum, c2, m, dim, d, rho, rhat, ess);
+    }
     return MMCMC_OK;
 }
 

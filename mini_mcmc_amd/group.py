@@ -8,12 +8,21 @@ way to use several GPUs; this one needs no launcher.)"""
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
 from . import _lib as L
 from . import checkpoint as K
 from .distributions import IsotropicGaussian, Target
+
+
+def bind_collectives(path, ranks_may_share_a_device: bool = False) -> None:
+    """mmcmc_group_bind_collectives: take ncclCommInitAll / ncclCommDestroy / ncclAllGather / ncclAllReduce from the library
+    at `path` instead of librccl.  Once per process, before the first group is created; ranks_may_share_a_device only for a
+    library that accepts several ranks on one device (then a device listed twice keeps the collective branch)."""
+    p = None if path is None else os.fsencode(path)
+    L.check(L.lib().mmcmc_group_bind_collectives(p, int(bool(ranks_may_share_a_device))), "mmcmc_group_bind_collectives")
 
 
 class _Group(K.Checkpointable):
