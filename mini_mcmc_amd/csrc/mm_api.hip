@@ -6,6 +6,7 @@
  * on the CPU and nothing here touches oracle/.
  */
 #include "../../include/mmcmc.h"
+#include "mm_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -25,47 +26,14 @@
 #include "mm_kernels.h"
 #include "mm_host_rng.h"
 #include "mm_params.h"
+#include "mm_path.h"
 #include "mm_wide.h"
 #include "mm_tuning.h"
 #include "mm_rtc.h"
 
 size_t mm_split_lds_bytes_f32(int dim, int mh); /* mm_inst_f32.hip */
 
-#define MM_HIP(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess)                                                                                     \
-            return (int)_e;                                                                                       \
-    } while (0)
-
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
-int check_device(int device)
-{
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return MMCMC_ERR_NO_DEVICE;
-    if (device < 0 || device >= n)
-        return MMCMC_ERR_INVALID_ARG;
-    return MMCMC_OK;
-}
 
 template <class T> const mm_kernel_entry<T> *table(int *n);
 template <> const mm_kernel_entry<float> *table<float>(int *n) { return mm_kernel_table_f32(n); }
@@ -175,16 +143,13 @@ struct Sampler {
     uint64_t seed = 0, chain_offset = 0;
     uint64_t iter = 0;
     uint32_t iters_per_launch = 0;
-    int variant = 2; /* mm_run_kernel PIPE: 0 plain; 2 (default) noise of two iterations packed + pipelined (PIPE = 1,
-                        noise of t+1 pipelined, measured equal to 2 and is no longer instantiated; 1 selects 2);
-                        3 = lane-group / MFMA kernel (mm_hmc_lg.h): HMC, f64, GaussianND of dim 16 or 32;
-                        5 = noise waves + transition waves (mm_split_kernels.h), the default for f32 up to dim 8 */
-    bool lg_ok = false;
-    const mm_user_target *user = nullptr; /* run-time compiled target (mm_rtc.hip), variant 7 */
-    bool generic = false;      /* no fixed-dimension kernel: the run-time-dimension path (mm_generic.h), variant 6 */
-    bool generic_ok = false;   /* the target kind has a run-time-dimension form */
-    bool wide_ok = false;      /* HMC with one chain per workgroup (mm_wide.hip): a huge dimension, variant 8 */
-    void *d_gscratch = nullptr; /* its HBM store when the chain vectors do not fit LDS */
+    mm_path_caps caps;        /* what decides the kernel path (mm_path.h), gathered once by sampler_create */
+    int variant = MM_VAR_PAIRED; /* MM_VAR_* (mm_path.h): 0 plain; 1 alias of 2; 2 paired + pipelined noise; 3 lane groups + MFMA
+                                    (HMC, GaussianND of dim 16 / 32); 5 noise waves + transition waves (up to dim 8, the f32
+                                    default); 6 run-time dimension; 7 run-time compiled unit; 8 wide (HMC, one chain per
+                                    workgroup).  Always one mm_variant_status allows; the default is mm_default_variant's */
+    const mm_user_target *user = nullptr; /* the run-time compiled unit (mm_rtc.hip) when caps.unit says there is one */
+    void *d_gscratch = nullptr; /* the run-time-dimension path's HBM store when the chain vectors do not fit LDS */
     void *d_stage = nullptr;    /* device staging of a sample that goes to the host (sampler_run) */
     size_t stage_cap = 0;
     size_t c_pad = 0;
@@ -297,7 +262,7 @@ int sampler_create(Sampler **out, int sampler, const mmcmc_target_desc *target, 
     int st = validate_target(target);
     if (st != MMCMC_OK)
         return st;
-    st = check_device(device);
+    st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
     Sampler *s = new (std::nothrow) Sampler();
@@ -311,50 +276,49 @@ int sampler_create(Sampler **out, int sampler, const mmcmc_target_desc *target, 
     s->n_chains = n_chains;
     s->scale = scale;
     s->n_leapfrog = n_leapfrog;
+    mm_path_caps &c = s->caps;
+    c.sampler = sampler;
+    c.dtype = dtype;
+    c.dim = s->dim;
+    auto entry_caps = [&c](const auto *k) {
+        c.fixed = k != nullptr;
+        c.split = k && k->run_mh_split && k->run_hmc_split && k->run_hmc_split10;
+        c.pp_sched = k && k->run_hmc_pp_sched;
+        c.split_sched = c.split && k->run_hmc_split_sched;
+    };
     if (dtype == MMCMC_F32)
-        s->kf = find_kernel<float>(s->kind, s->dim);
+        entry_caps(s->kf = find_kernel<float>(s->kind, s->dim));
     else
-        s->kd = find_kernel<double>(s->kind, s->dim);
-    s->generic_ok = mm_generic_kind_ok(s->kind);
+        entry_caps(s->kd = find_kernel<double>(s->kind, s->dim));
+    c.generic_ok = mm_generic_kind_ok(s->kind);
+    /* the run-time-dimension path keeps a chain's vectors in LDS when they fit */
+    c.generic_lds = c.generic_ok && (dtype == MMCMC_F32 ? mm_generic_store_bytes<float>(sampler, s->dim)
+                                                        : mm_generic_store_bytes<double>(sampler, s->dim)) <= MM_GENERIC_LDS_MAX;
     s->user = s->kind >= MM_USER_KIND_BASE ? mm_rtc_find(s->kind) : nullptr;
     if (s->user) {
-        s->variant = 7;
-    } else if (!s->kf && !s->kd) {
+        c.unit = MM_UNIT_CALLER;
+    } else if (!c.fixed) {
         /* a dimension without a register-resident kernel: the run-time-dimension path */
-        if (!s->generic_ok) {
+        if (!c.generic_ok) {
             delete s;
             return MMCMC_ERR_UNSUPPORTED;
         }
-        s->generic = true;
-        s->variant = 6;
         /* up to dimension 32 the target's own functor is compiled into the register-resident skeletons on first use
          * (hipRTC, mm_rtc_builtin): variant 7 then, with the run-time-D kernel (6) still selectable */
         if (s->dim <= 32) {
-            DeviceGuard gb(device);
+            DevGuard gb(device);
             s->user = mm_rtc_builtin(s->kind, s->dim);
             if (s->user)
-                s->variant = 7;
+                c.unit = MM_UNIT_BUILTIN;
         }
     }
     /* dense Gaussian at dim 16 / 32 under HMC (f64 and f32): the lane-group / MFMA kernels, and the default there */
-    s->lg_ok = sampler == MM_SAMPLER_HMC && s->kind == MMCMC_GAUSSIAN_ND && (s->dim == 16 || s->dim == 32);
-    /* at dim 32 the paired / pipelined form holds four noise vectors next to the state and spills: the plain form
-     * is twice as fast there (RosenbrockND(32) f32: 1.0 ms vs 2.2 ms for run(100, 20) of 65 536 chains) */
-    if (s->dim > 16 && !s->generic && !s->user)
-        s->variant = 0;
-    /* f32 up to dim 8: noise waves + transition waves, four waves per SIMD (mm_split_kernels.h; config 3: 0.192 ms
-     * against 0.268 ms for variant 2) */
-    if (dtype == MMCMC_F32 && s->kf && s->kf->run_mh_split)
-        s->variant = 5;
-    if (s->lg_ok)
-        s->variant = 3;
-    if (s->user && !s->generic)
-        s->variant = 7;
+    c.lg_ok = sampler == MM_SAMPLER_HMC && s->kind == MMCMC_GAUSSIAN_ND && (s->dim == 16 || s->dim == 32);
     /* few chains of a huge dimension (hmc.rs:882-916: 6 x 10 000): the coordinates of a chain across a workgroup */
-    s->wide_ok = sampler == MM_SAMPLER_HMC && !s->user && mm_wide_kind_ok(s->kind) && s->dim >= 4 && s->dim <= MM_WIDE_MAX_DIM;
-    if (s->wide_ok && s->generic && s->dim >= 128 && n_chains < 1024)
-        s->variant = 8;
-    DeviceGuard g(device);
+    c.wide_ok = sampler == MM_SAMPLER_HMC && !s->user && mm_wide_kind_ok(s->kind) && s->dim >= 4 && s->dim <= MM_WIDE_MAX_DIM;
+    c.few_chains = s->dim >= 128 && n_chains < 1024;
+    s->variant = mm_default_variant(c);
+    DevGuard g(device);
     auto fail = [&](int code) {
         if (s->d_state)
             (void)hipFree(s->d_state);
@@ -393,15 +357,12 @@ int sampler_create(Sampler **out, int sampler, const mmcmc_target_desc *target, 
     if ((e = hipMemcpy(s->d_state, init, bytes, hipMemcpyHostToDevice)) != hipSuccess)
         return fail((int)e);
     s->c_pad = (n_chains + 63) / 64 * 64;
-    if (s->generic_ok) {
+    if (mm_path_generic(c) && !c.generic_lds) {
         /* the run-time-dimension path (default without a fixed-dimension kernel, selectable as variant 6 otherwise)
          * keeps a chain's vectors in LDS when they fit, else in this lane-interleaved HBM store */
-        const size_t lds = dtype == MMCMC_F32 ? mm_generic_store_bytes<float>(sampler, s->dim) : mm_generic_store_bytes<double>(sampler, s->dim);
-        if (lds > MM_GENERIC_LDS_MAX && s->generic) {
-            const size_t nvec = sampler == MM_SAMPLER_HMC ? MM_GV_HMC : MM_GV_MH;
-            if ((e = hipMalloc(&s->d_gscratch, nvec * (size_t)s->dim * s->c_pad * s->esize())) != hipSuccess)
-                return fail((int)e);
-        }
+        const size_t nvec = sampler == MM_SAMPLER_HMC ? MM_GV_HMC : MM_GV_MH;
+        if ((e = hipMalloc(&s->d_gscratch, nvec * (size_t)s->dim * s->c_pad * s->esize())) != hipSuccess)
+            return fail((int)e);
     }
     if ((e = hipMalloc((void **)&s->d_accept, n_chains * sizeof(unsigned long long))) != hipSuccess)
         return fail((int)e);
@@ -415,9 +376,10 @@ int sampler_create(Sampler **out, int sampler, const mmcmc_target_desc *target, 
         return fail((int)e);
     if ((e = hipEventCreate(&s->ev1)) != hipSuccess)
         return fail((int)e);
-    if (s->user && s->generic && !g_in_unit_check && !builtin_unit_verified(s->user, sampler, target, dtype, device)) {
+    if (c.unit == MM_UNIT_BUILTIN && !g_in_unit_check && !builtin_unit_verified(s->user, sampler, target, dtype, device)) {
         s->user = nullptr; /* the run-time-dimension kernel only (set_kernel_variant(7) is refused then) */
-        s->variant = 6;
+        c.unit = MM_UNIT_NONE;
+        s->variant = MM_VAR_GENERIC;
     }
     *out = s;
     return MMCMC_OK;
@@ -427,7 +389,7 @@ int sampler_destroy(Sampler *s)
 {
     if (!s)
         return MMCMC_ERR_INVALID_ARG;
-    DeviceGuard g(s->device);
+    DevGuard g(s->device);
     (void)hipStreamSynchronize(s->stream);
     (void)hipFree(s->d_state);
     if (s->d_mat)
@@ -460,6 +422,25 @@ static size_t mm_tile_lds_bytes_rt(size_t esz, int D)
     return (esz == 4 ? (size_t)MM_NOISE_TABLE_BYTES : 0) + (size_t)64 * stride * esz;
 }
 
+/* the fields every kernel argument struct has under the same name, from the run's mm_run_args */
+template <class Q, class T> Q shared_args(const mm_run_args<T> &a)
+{
+    Q q;
+    q.state = a.state;
+    q.out = a.out;
+    q.accept = a.accept;
+    q.accept_total = a.accept_total;
+    q.n_chains = a.n_chains;
+    q.seed = a.seed;
+    q.chain_offset = a.chain_offset;
+    q.n_total = a.n_total;
+    q.iter0 = a.iter0;
+    q.n_discard = a.n_discard;
+    q.n_collect = a.n_collect;
+    q.out_t0 = a.out_t0;
+    return q;
+}
+
 template <class T>
 int launch_range(Sampler *s, const mm_kernel_entry<T> *k, const mm_tparams<T> &P, T *d_out, size_t n_total,
                  uint32_t n_discard, uint32_t n_collect, uint32_t out_t0, hipStream_t stream)
@@ -480,18 +461,36 @@ int launch_range(Sampler *s, const mm_kernel_entry<T> *k, const mm_tparams<T> &P
     a.n_collect = n_collect;
     a.out_t0 = out_t0;
     a.n_total = n_total;
-    unsigned int grid = (unsigned int)((s->n_chains + s->block - 1) / s->block);
-    hipError_t e;
+    const unsigned int grid = (unsigned int)((s->n_chains + s->block - 1) / s->block);
+    hipError_t e = hipErrorNotFound;
     const bool mh = s->sampler == MM_SAMPLER_MH, l10 = s->n_leapfrog == 10;
-    if (s->sched_run) {
-        /* a scheduled run on a variant with a scheduled kernel (sched_kernel_ok): (eps, L) per transition from the device */
-        const mm_sched_step<T> *sched = (const mm_sched_step<T> *)s->sched_run;
-        e = s->variant == 5 ? k->run_hmc_split_sched(a, sched, s->sched_iter0, stream)
-                            : k->run_hmc_pp_sched(a, sched, s->sched_iter0, grid, s->block, stream);
-    } else if (s->variant == 7 && s->user) {
+    const mm_sched_step<T> *sched = (const mm_sched_step<T> *)s->sched_run;
+    switch (mm_launch_path(s->caps, s->variant, s->n_leapfrog, sched != nullptr)) {
+    case MM_LAUNCH_PLAIN:
+        e = mh ? k->run_mh(a, grid, s->block, stream) : k->run_hmc(a, grid, s->block, stream);
+        break;
+    case MM_LAUNCH_PP:
+        e = mh ? k->run_mh_pp(a, grid, s->block, stream) : k->run_hmc_pp(a, grid, s->block, stream);
+        break;
+    case MM_LAUNCH_PP10:
+        e = k->run_hmc_pp10(a, grid, s->block, stream);
+        break;
+    case MM_LAUNCH_SPLIT:
+        e = mh ? k->run_mh_split(a, stream) : k->run_hmc_split(a, stream);
+        break;
+    case MM_LAUNCH_SPLIT10:
+        e = k->run_hmc_split10(a, stream);
+        break;
+    /* a scheduled run on a variant with a scheduled kernel: (eps, L) per transition from the device */
+    case MM_LAUNCH_PP_SCHED:
+        e = k->run_hmc_pp_sched(a, sched, s->sched_iter0, grid, s->block, stream);
+        break;
+    case MM_LAUNCH_SPLIT_SCHED:
+        e = k->run_hmc_split_sched(a, sched, s->sched_iter0, stream);
+        break;
+    case MM_LAUNCH_UNIT: {
         /* the same skeleton (mm_run_kernel_body, PIPE = 2) around the user's functor, from the run-time compiled module */
         /* f32 up to dim 8: the split-role skeleton (four waves per SIMD) where the module has it; else PIPE = 2, one wave per SIMD */
-        e = hipErrorNotFound;
         const char *us = mm_tuning_env("MMCMC_USER_SPLIT"); /* measurement aid: "0" keeps the one-wave-per-SIMD skeleton */
         if (std::is_same<T, float>::value && s->dim <= 8 && !(us && us[0] == '0')) {
             const size_t lds_split = mm_split_lds_bytes_f32(s->dim, mh ? 1 : 0);
@@ -506,116 +505,55 @@ int launch_range(Sampler *s, const mm_kernel_entry<T> *k, const mm_tparams<T> &P
             const size_t lds = mm_tile_lds_bytes_rt(sizeof(T), s->dim);
             e = mm_rtc_launch_run(s->user, mh ? 0 : 1, std::is_same<T, float>::value ? 0 : 1, &a, sizeof(a), grid, s->block, lds, stream);
         }
-    } else if (s->variant == 8 && s->wide_ok) {
-        mm_wide_args<T> q;
+        break;
+    }
+    case MM_LAUNCH_WIDE: {
+        auto q = shared_args<mm_wide_args<T>>(a);
         q.P = P;
         q.kind = s->kind;
         q.dim = s->dim;
         q.eps = (T)s->scale;
         q.n_leapfrog = s->n_leapfrog;
-        q.state = (T *)s->d_state;
-        q.out = d_out;
-        q.accept = a.accept;
-        q.accept_total = a.accept_total;
-        q.n_chains = a.n_chains;
-        q.seed = a.seed;
-        q.chain_offset = a.chain_offset;
-        q.n_total = n_total;
-        q.iter0 = a.iter0;
-        q.n_discard = n_discard;
-        q.n_collect = n_collect;
-        q.out_t0 = out_t0;
         if constexpr (std::is_same<T, float>::value)
             e = mm_launch_hmc_wide_f32(q, stream);
         else
             e = mm_launch_hmc_wide_f64(q, stream);
-    } else if (s->variant == 6) {
-        mm_gen_args<T> q;
+        break;
+    }
+    case MM_LAUNCH_GENERIC: {
+        auto q = shared_args<mm_gen_args<T>>(a);
         q.P = P;
         q.kind = s->kind;
         q.dim = s->dim;
         q.sampler = mh ? 0 : 1;
         q.scale = (T)s->scale;
         q.n_leapfrog = s->n_leapfrog;
-        q.state = (T *)s->d_state;
-        q.out = d_out;
-        q.accept = a.accept;
-        q.accept_total = a.accept_total;
         q.scratch = (T *)s->d_gscratch;
-        q.n_chains = a.n_chains;
         q.c_pad = s->c_pad;
-        q.seed = a.seed;
-        q.chain_offset = a.chain_offset;
-        q.n_total = n_total;
-        q.iter0 = a.iter0;
-        q.n_discard = n_discard;
-        q.n_collect = n_collect;
-        q.out_t0 = out_t0;
         if constexpr (std::is_same<T, float>::value)
             e = mm_launch_run_generic_f32(q, stream);
         else
             e = mm_launch_run_generic_f64(q, stream);
-    } else if (s->variant == 3 && s->lg_ok) {
-        if constexpr (std::is_same<T, double>::value) {
-            mm_hmc_lg_args q;
-            q.mat = (const double *)s->d_mat;
-            q.state = (double *)s->d_state;
-            q.out = (double *)d_out;
-            q.accept = a.accept;
-            q.accept_total = a.accept_total;
-            q.n_chains = a.n_chains;
-            q.seed = a.seed;
-            q.chain_offset = a.chain_offset;
-            q.n_total = n_total;
-            q.iter0 = a.iter0;
-            q.n_discard = n_discard;
-            q.n_collect = n_collect;
-            q.out_t0 = out_t0;
-            q.eps = s->scale;
-            q.n_leapfrog = s->n_leapfrog;
+        break;
+    }
+    case MM_LAUNCH_LG: {
+        auto q = shared_args<std::conditional_t<std::is_same<T, double>::value, mm_hmc_lg_args, mm_hmc_lg32_args>>(a);
+        q.mat = (const T *)s->d_mat;
+        q.eps = s->scale;
+        q.n_leapfrog = s->n_leapfrog;
+        if constexpr (std::is_same<T, double>::value)
             e = mm_launch_hmc_lg(s->dim, q, stream);
-        } else {
-            mm_hmc_lg32_args q;
-            q.mat = (const float *)s->d_mat;
-            q.state = (float *)s->d_state;
-            q.out = (float *)d_out;
-            q.accept = a.accept;
-            q.accept_total = a.accept_total;
-            q.n_chains = a.n_chains;
-            q.seed = a.seed;
-            q.chain_offset = a.chain_offset;
-            q.n_total = n_total;
-            q.iter0 = a.iter0;
-            q.n_discard = n_discard;
-            q.n_collect = n_collect;
-            q.out_t0 = out_t0;
-            q.eps = s->scale;
-            q.n_leapfrog = s->n_leapfrog;
+        else
             e = mm_launch_hmc_lg32(s->dim, q, stream);
-        }
-    } else if (s->variant == 5) {
-        /* noise waves + transition waves (mm_split_kernels.h); the setter has checked that the instance exists */
-        e = mh ? k->run_mh_split(a, stream) : (l10 ? k->run_hmc_split10(a, stream) : k->run_hmc_split(a, stream));
-    } else if (s->variant != 0)
-        e = mh ? k->run_mh_pp(a, grid, s->block, stream)
-               : (l10 ? k->run_hmc_pp10(a, grid, s->block, stream) : k->run_hmc_pp(a, grid, s->block, stream));
-    else
-        e = mh ? k->run_mh(a, grid, s->block, stream) : k->run_hmc(a, grid, s->block, stream);
+        break;
+    }
+    case MM_LAUNCH_SEGMENTED: /* sampler_run runs such a schedule as unscheduled launches: sched_run is never set for it */
+        return MMCMC_ERR_STATE;
+    }
     if (e != hipSuccess)
         return (int)e;
     s->iter += (uint64_t)n_discard + n_collect;
     return MMCMC_OK;
-}
-
-/* does the handle's variant have a kernel that reads (eps, L) per transition?  The split kernel (5, f32 up to dim 8) and
- * PIPE = 2 (2, and 1 which selects it) of the fixed-dimension targets; every other variant runs a schedule in segments */
-template <class T> bool sched_kernel_ok(const Sampler *s, const mm_kernel_entry<T> *k)
-{
-    if (s->sampler != MM_SAMPLER_HMC || !k || (s->user && s->variant == 7))
-        return false;
-    if (s->variant == 5)
-        return k->run_hmc_split_sched != nullptr;
-    return (s->variant == 1 || s->variant == 2) && k->run_hmc_pp_sched != nullptr;
 }
 
 /* the schedule of a run as mm_sched_step<T> [n + 1] in the handle's device buffer; eps converted as launch_range converts
@@ -670,7 +608,7 @@ int sampler_run(Sampler *s, size_t n_collect, size_t n_discard, void *out, int o
         return MMCMC_ERR_INVALID_ARG;
     if ((uint64_t)n_total_rows * (uint64_t)s->dim >= (1ull << 30) || s->iter + n_collect + n_discard >= (1ull << 32))
         return MMCMC_ERR_SHAPE;
-    DeviceGuard g(s->device);
+    DevGuard g(s->device);
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : s->stream;
     /* a scheduled run: restores the handle's (eps, L) and leaves launch_range's scheduled mode however it returns */
     struct SchedScope {
@@ -685,7 +623,7 @@ int sampler_run(Sampler *s, size_t n_collect, size_t n_discard, void *out, int o
         }
     } sched_scope{s, s->scale, s->n_leapfrog};
     const bool sched = sched_eps != nullptr;
-    if (sched && (s->dtype == MMCMC_F32 ? sched_kernel_ok<float>(s, s->kf) : sched_kernel_ok<double>(s, s->kd))) {
+    if (sched && mm_launch_path(s->caps, s->variant, s->n_leapfrog, true) != MM_LAUNCH_SEGMENTED) {
         const int st = s->dtype == MMCMC_F32 ? upload_schedule<float>(s, sched_eps, sched_L, n_collect + n_discard, stream)
                                              : upload_schedule<double>(s, sched_eps, sched_L, n_collect + n_discard, stream);
         if (st != MMCMC_OK)
@@ -781,7 +719,7 @@ int sampler_state(Sampler *s, void *out)
 {
     if (!s || !out)
         return MMCMC_ERR_INVALID_ARG;
-    DeviceGuard g(s->device);
+    DevGuard g(s->device);
     MM_HIP(hipStreamSynchronize(s->stream));
     MM_HIP(hipDeviceSynchronize());
     MM_HIP(hipMemcpy(out, s->d_state, s->n_chains * (size_t)s->dim * s->esize(), hipMemcpyDeviceToHost));
@@ -795,7 +733,7 @@ int sampler_set_state(Sampler *s, const void *positions, int is_device, void *st
 {
     if (!s || !positions)
         return MMCMC_ERR_INVALID_ARG;
-    DeviceGuard g(s->device);
+    DevGuard g(s->device);
     if (is_device) {
         hipPointerAttribute_t attr{};
         if (hipPointerGetAttributes(&attr, positions) != hipSuccess) {
@@ -839,7 +777,7 @@ int sampler_sync(Sampler *s)
 {
     if (!s)
         return MMCMC_ERR_INVALID_ARG;
-    DeviceGuard g(s->device);
+    DevGuard g(s->device);
     if (s->timed)
         MM_HIP(hipEventSynchronize(s->ev1));
     MM_HIP(hipStreamSynchronize(s->stream));
@@ -852,7 +790,7 @@ int sampler_timing(Sampler *s, mmcmc_timing *t)
         return MMCMC_ERR_INVALID_ARG;
     if (!s->timed)
         return MMCMC_ERR_STATE; /* no timed run yet */
-    DeviceGuard g(s->device);
+    DevGuard g(s->device);
     MM_HIP(hipEventSynchronize(s->ev1));
     float ms = 0.f;
     MM_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
@@ -1104,69 +1042,21 @@ int mmcmc_mh_set_chain_offset(mmcmc_mh *h, uint64_t off)
     h->s->chain_offset = off;
     return MMCMC_OK;
 }
-/* variant 5 (noise waves + transition waves, two to four waves per SIMD) exists up to dim 8 */
-static bool split_ok(const Sampler *s)
+/* which variants a handle takes: mm_variant_status (mm_path.h), the MH and HMC ranges included */
+static int sampler_set_variant(Sampler *s, int variant)
 {
-    return s->dtype == MMCMC_F32 ? (s->kf && s->kf->run_mh_split) : (s->kd && s->kd->run_mh_split);
-}
-/* variant 6 = the run-time-dimension path: always for dimensions without a fixed kernel (then the only variant); on
- * request wherever the target kind has one and the chain vectors fit LDS (what the bit-identity tests use) */
-static int set_variant_common(Sampler *s, int variant)
-{
-    if (s->user && s->generic) { /* a built-in target on its run-time compiled register kernels (7) or the run-time-D kernel (6) */
-        if (variant != 6 && variant != 7)
-            return MMCMC_ERR_UNSUPPORTED;
+    const int st = mm_variant_status(s->caps, variant);
+    if (st == MMCMC_OK)
         s->variant = variant;
-        return MMCMC_OK;
-    }
-    if (s->user)
-        return variant == 7 ? MMCMC_OK : MMCMC_ERR_UNSUPPORTED;
-    if (variant == 8) {
-        if (!s->wide_ok)
-            return MMCMC_ERR_UNSUPPORTED;
-        s->variant = 8;
-        return MMCMC_OK;
-    }
-    if (s->generic) {
-        if (variant != 6)
-            return MMCMC_ERR_UNSUPPORTED;
-        s->variant = 6;
-        return MMCMC_OK;
-    }
-    if (variant == 6) {
-        const size_t lds = s->dtype == MMCMC_F32 ? mm_generic_store_bytes<float>(s->sampler, s->dim)
-                                                 : mm_generic_store_bytes<double>(s->sampler, s->dim);
-        if (!s->generic_ok || lds > MM_GENERIC_LDS_MAX)
-            return MMCMC_ERR_UNSUPPORTED;
-        s->variant = 6;
-        return MMCMC_OK;
-    }
-    return 1; /* not handled here */
+    return st;
 }
-
 int mmcmc_mh_set_kernel_variant(mmcmc_mh *h, int variant)
 {
-    if (!h || variant < 0 || (variant > 2 && variant != 5 && variant != 6 && variant != 7))
-        return MMCMC_ERR_INVALID_ARG;
-    if (const int st = set_variant_common(h->s, variant); st <= 0)
-        return st;
-    if (variant == 5 && !split_ok(h->s))
-        return MMCMC_ERR_UNSUPPORTED;
-    h->s->variant = variant;
-    return MMCMC_OK;
+    return h ? sampler_set_variant(h->s, variant) : MMCMC_ERR_INVALID_ARG;
 }
 int mmcmc_hmc_set_kernel_variant(mmcmc_hmc *h, int variant)
 {
-    if (!h || variant < 0 || (variant > 3 && variant != 5 && variant != 6 && variant != 7 && variant != 8))
-        return MMCMC_ERR_INVALID_ARG;
-    if (const int st = set_variant_common(h->s, variant); st <= 0)
-        return st;
-    if (variant == 3 && !h->s->lg_ok)
-        return MMCMC_ERR_UNSUPPORTED;
-    if (variant == 5 && !split_ok(h->s))
-        return MMCMC_ERR_UNSUPPORTED;
-    h->s->variant = variant;
-    return MMCMC_OK;
+    return h ? sampler_set_variant(h->s, variant) : MMCMC_ERR_INVALID_ARG;
 }
 int mmcmc_hmc_kernel_variant(mmcmc_hmc *h) { return h ? h->s->variant : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_mh_enable_timing(mmcmc_mh *h, int on)
@@ -1390,10 +1280,10 @@ int mmcmc_logp_grad_batch(const mmcmc_target_desc *target, int dtype, const void
     int st = validate_target(target);
     if (st != MMCMC_OK)
         return st;
-    st = check_device(device);
+    st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
-    DeviceGuard g(device);
+    DevGuard g(device);
     return dtype == MMCMC_F32 ? logp_grad_batch_t<float>(target, x, n, logp, grad)
                               : logp_grad_batch_t<double>(target, x, n, logp, grad);
 }
@@ -1403,10 +1293,10 @@ int mmcmc_draw_noise(uint64_t seed, uint64_t chain_offset, uint32_t iteration, s
 {
     if (!z || !u || n_chains == 0 || dim <= 0 || (dtype != MMCMC_F32 && dtype != MMCMC_F64))
         return MMCMC_ERR_INVALID_ARG;
-    int st = check_device(device);
+    int st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
-    DeviceGuard g(device);
+    DevGuard g(device);
     return dtype == MMCMC_F32 ? draw_noise_t<float>(seed, chain_offset, iteration, n_chains, dim, z, u)
                               : draw_noise_t<double>(seed, chain_offset, iteration, n_chains, dim, z, u);
 }
@@ -1416,10 +1306,10 @@ int mmcmc_draw_noise_mh(uint64_t seed, uint64_t chain_offset, uint32_t iteration
 {
     if (!z || !u || n_chains == 0 || dim <= 0 || (dtype != MMCMC_F32 && dtype != MMCMC_F64))
         return MMCMC_ERR_INVALID_ARG;
-    int st = check_device(device);
+    int st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
-    DeviceGuard g(device);
+    DevGuard g(device);
     return dtype == MMCMC_F32 ? draw_noise_t<float>(seed, chain_offset, iteration, n_chains, dim, z, u, 1)
                               : draw_noise_t<double>(seed, chain_offset, iteration, n_chains, dim, z, u, 1);
 }

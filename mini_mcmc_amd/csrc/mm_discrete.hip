@@ -5,6 +5,7 @@
  * per wave in LDS (64 chains x 64 iterations) and written as 256-byte rows.
  */
 #include "../../include/mmcmc.h"
+#include "mm_host.h"
 #include "mm_hostcopy.h"
 
 #include <hip/hip_runtime.h>
@@ -19,29 +20,7 @@
 #include "mm_kernels.h"
 #include "mm_rtc.h"
 
-#define MM_HIP(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess)                                                                                     \
-            return (int)_e;                                                                                       \
-    } while (0)
-
 namespace {
-
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        (void)hipSetDevice(d);
-    }
-    ~DevGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
 
 struct run_args {
     mm_discrete_params P;

@@ -22,6 +22,7 @@
  * ranks on one device, a device listed twice keeps the collective branch (tests/c/fake_collectives.c: N > 1 ranks on one GPU).
  */
 #include "../../include/mmcmc.h"
+#include "mm_host.h"
 #include "mm_hostcopy.h"
 
 #include <dlfcn.h>
@@ -461,8 +462,7 @@ int group_run(Group *g, size_t n_collect, size_t n_discard, void *out_host, uint
     if (async) {
         if (g->sampler == 2)
             return MMCMC_ERR_UNSUPPORTED; /* NUTS hands adaptation state over between its launches: blocking only */
-        int prev = -1;
-        (void)hipGetDevice(&prev);
+        DevGuard restore; /* the loops below set each shard's device */
         int st = MMCMC_OK;
         /* every allocation first: a failure here has advanced no shard */
         for (Shard &s : g->sh) {
@@ -494,8 +494,6 @@ int group_run(Group *g, size_t n_collect, size_t n_discard, void *out_host, uint
                     (void)hipStreamSynchronize(g->sh[i].stream);
             g->broken = true;
         }
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
         if (st == MMCMC_OK)
             g->last_collect = n_collect;
         return st;
@@ -540,8 +538,7 @@ int group_sync(Group *g)
 {
     if (!g)
         return MMCMC_ERR_INVALID_ARG;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
+    DevGuard restore;
     int st = MMCMC_OK;
     for (Shard &s : g->sh) {
         hipError_t e = hipSetDevice(s.device);
@@ -550,8 +547,6 @@ int group_sync(Group *g)
         if (e != hipSuccess && st == MMCMC_OK)
             st = (int)e;
     }
-    if (prev >= 0)
-        (void)hipSetDevice(prev);
     return st;
 }
 
@@ -562,8 +557,7 @@ int group_stream_timer(Group *g, int stop, float *ms)
 {
     if (!g || (stop && !ms))
         return MMCMC_ERR_INVALID_ARG;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
+    DevGuard restore;
     hipError_t e = hipSuccess;
     for (Shard &s : g->sh) {
         if ((e = hipSetDevice(s.device)) != hipSuccess)
@@ -584,8 +578,6 @@ int group_stream_timer(Group *g, int stop, float *ms)
             ++i;
         }
     }
-    if (prev >= 0)
-        (void)hipSetDevice(prev);
     return e == hipSuccess ? MMCMC_OK : (int)e;
 }
 

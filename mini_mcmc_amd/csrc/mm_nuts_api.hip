@@ -3,6 +3,7 @@
  * Mirrors NUTS::{new, set_seed, run, run_progress} (nuts.rs:123-170, 194-353) over NUTSChain (nuts.rs:410-691).
  */
 #include "../../include/mmcmc.h"
+#include "mm_host.h"
 #include "mm_hostcopy.h"
 
 #include <hip/hip_runtime.h>
@@ -25,29 +26,7 @@
 #include "mm_rtc.h"
 #include "mm_params.h"
 
-#define MM_HIP(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess)                                                                                     \
-            return (int)_e;                                                                                       \
-    } while (0)
-
 namespace {
-
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        (void)hipSetDevice(d);
-    }
-    ~DevGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
 
 /* 0: normal; 1: inside the self-test of a run-time compiled unit; 2: create without run-time compiled built-in units */
 thread_local int g_rtc_create_mode = 0;

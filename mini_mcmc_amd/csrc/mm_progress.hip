@@ -14,6 +14,7 @@
  * called after every `every` transitions (0 = ten times per run) with the two numbers the reference's bar shows.
  * Host-only code over the public C ABI (mmcmc_*_run_rows, mmcmc_tracker_*, mmcmc_run_stats_from): no kernels here. */
 #include "../../include/mmcmc.h"
+#include "mm_host.h"
 #include "mm_hostcopy.h"
 
 #include <hip/hip_runtime.h>
@@ -24,16 +25,6 @@
 #include <vector>
 
 namespace {
-
-struct DevGuard {
-    int prev = 0;
-    explicit DevGuard(int d)
-    {
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(d);
-    }
-    ~DevGuard() { (void)hipSetDevice(prev); }
-};
 
 struct DevBuf {
     void *p = nullptr;

@@ -27,6 +27,7 @@
  * histograms).  Single device: ranks are global over chains, device groups are out of scope.
  */
 #include "../../include/mmcmc.h"
+#include "mm_host.h"
 #include "mm_rank.h"
 
 #include <hip/hip_runtime.h>
@@ -392,38 +393,6 @@ __global__ __launch_bounds__(256) void mm_rank_indicator_kernel(const T *__restr
 
 /* ---- host ---- */
 
-#define MM_HIP(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess)                                                                                     \
-            return (int)_e;                                                                                       \
-    } while (0)
-
-int rank_check_device(int device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return MMCMC_ERR_NO_DEVICE;
-    if (device < 0 || device >= n)
-        return MMCMC_ERR_INVALID_ARG;
-    return MMCMC_OK;
-}
-
-struct RankDevGuard {
-    int prev = -1;
-    explicit RankDevGuard(int d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        (void)hipSetDevice(d);
-    }
-    ~RankDevGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
 /* every device buffer of a call; freed when the call returns (each entry point ends with a stream synchronise) */
 struct RankBufs {
     std::vector<void *> owned;
@@ -584,9 +553,9 @@ int mmcmc_rank_normalize(const void *sample, int sample_is_device, int dtype, si
         st = MMCMC_ERR_INVALID_ARG;
     if (st != MMCMC_OK)
         return st;
-    if ((st = rank_check_device(device)) != MMCMC_OK)
+    if ((st = mm_check_device(device)) != MMCMC_OK)
         return st;
-    RankDevGuard g(device);
+    DevGuard g(device);
     hipStream_t stream = (hipStream_t)stream_v;
     const size_t S = n_chains * n, total = S * dim;
     RankBufs bufs;
@@ -638,11 +607,11 @@ int mmcmc_quantiles(const void *sample, int sample_is_device, int dtype, size_t 
         st = MMCMC_ERR_INVALID_ARG;
     if (st != MMCMC_OK)
         return st;
-    if ((st = rank_check_device(device)) != MMCMC_OK)
+    if ((st = mm_check_device(device)) != MMCMC_OK)
         return st;
     if (n_probs == 0)
         return MMCMC_OK;
-    RankDevGuard g(device);
+    DevGuard g(device);
     hipStream_t stream = (hipStream_t)stream_v;
     const size_t S = n_chains * n, total = S * dim;
     RankBufs bufs;
@@ -677,9 +646,9 @@ int mmcmc_rank_diagnostics(const void *sample, int sample_is_device, int dtype, 
         st = MMCMC_ERR_SHAPE;
     if (st != MMCMC_OK)
         return st;
-    if ((st = rank_check_device(device)) != MMCMC_OK)
+    if ((st = mm_check_device(device)) != MMCMC_OK)
         return st;
-    RankDevGuard g(device);
+    DevGuard g(device);
     hipStream_t stream = (hipStream_t)stream_v;
     const size_t S = n_chains * n, total = S * dim;
     RankBufs bufs;

@@ -23,6 +23,7 @@
  * former, all-reduce of the latter; mini_mcmc_amd/stats.py).
  */
 #include "../../include/mmcmc.h"
+#include "mm_host.h"
 #include "mm_stats_fft.h"
 #include "mm_tuning.h"
 
@@ -36,13 +37,6 @@
 #include <cstring>
 #include <atomic>
 #include <vector>
-
-#define MM_HIP(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess)                                                                                     \
-            return (int)_e;                                                                                       \
-    } while (0)
 
 namespace {
 
@@ -1674,31 +1668,6 @@ __global__ void mm_parts_sum_kernel(const float *__restrict__ parts, unsigned in
     out[i] = t;
 }
 
-int check_device(int device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return MMCMC_ERR_NO_DEVICE;
-    if (device < 0 || device >= n)
-        return MMCMC_ERR_INVALID_ARG;
-    return MMCMC_OK;
-}
-
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        (void)hipSetDevice(d);
-    }
-    ~DevGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
 } // namespace
 
 /* number of waves (= per-wave lag-sum slabs) the half-chain kernel is launched with */
@@ -1970,7 +1939,7 @@ static int stats_partials_impl(const void *sample, int dtype, size_t n_chains, s
     const size_t m = n / 2;
     if (m < 1 || n >= (1ull << 31) || dim >= (1u << 16) || !stats_bins_fit(n, dim))
         return MMCMC_ERR_SHAPE;
-    int st = check_device(device);
+    int st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
     DevGuard g(device);
@@ -2344,7 +2313,7 @@ int mmcmc_stats_partials(const void *sample, int dtype, size_t n_chains, size_t 
         return MMCMC_ERR_INVALID_ARG;
     if (n >= (1ull << 31) || dim >= (1u << 16) || !stats_bins_fit(n, dim))
         return MMCMC_ERR_SHAPE;
-    int st = check_device(device);
+    int st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
     DevGuard g(device);
@@ -2457,7 +2426,7 @@ int mmcmc_split_rhat_mean_ess(const void *sample, int sample_is_device, int dtyp
     const size_t m = n / 2;
     if (m < 1 || n >= (1ull << 31) || dim >= (1u << 16) || !stats_bins_fit(n, dim))
         return MMCMC_ERR_SHAPE;
-    int st = check_device(device);
+    int st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
     DevGuard g(device);
@@ -2566,7 +2535,7 @@ int mmcmc_ess_from_chainstats(const void *sample, int sample_is_device, int dtyp
         return st;
     if (tc != n_chains || td != dim)
         return MMCMC_ERR_SHAPE;
-    st = check_device(device);
+    st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
     std::vector<float> within(dim), var(dim);

@@ -23,6 +23,7 @@
  *                 (the reference sums f32 in ndarray's order; parity to ~1e-6 relative, tests/test_tracker.py).
  */
 #include "../../include/mmcmc.h"
+#include "mm_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -31,33 +32,11 @@
 #include <vector>
 #include "mm_tuning.h"
 
-#define MM_HIP(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess)                                                                                     \
-            return (int)_e;                                                                                       \
-    } while (0)
-
 namespace {
 
 constexpr float kAlpha = 0.01f;      /* stats.rs:13 */
 constexpr size_t kTail = 16384;      /* flags replayed sequentially for p_accept */
 constexpr int kMaxDim = 64;
-
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        (void)hipSetDevice(d);
-    }
-    ~DevGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
 
 /* states [C, n_rows, D] of T; this call consumes rows t0 .. t0+k-1 of every chain; n_before = steps taken so far */
 template <class T>

@@ -47,7 +47,14 @@ class HMC(_Sampler):
 
     @property
     def kernel_variant(self) -> int:
-        """0 / 2: one chain per lane (plain / paired noise); 3: lane groups + MFMA (f64 GaussianND of dim 16 or 32)."""
+        """The variant in use (set_kernel_variant takes the same numbers; results do not depend on it).  One chain per lane:
+        0 plain, 2 noise of two iterations paired + pipelined (1 is kept as an alias: stored and reported as 1, runs as 2),
+        5 noise waves + transition waves (up to dim 8; the f32 default there).  3: lane groups + MFMA (GaussianND of dim 16
+        or 32, where it is the default).  6: run-time dimension (the default without a fixed-dimension kernel: dims other
+        than 1..8, 16, 32; selectable elsewhere while a chain's vectors fit LDS).  7: a run-time compiled unit -- a
+        UserTarget's only variant, and the default of a built-in target at dims 9..31, where 6 stays selectable.
+        8: wide, one chain per workgroup (IsotropicGaussian, RosenbrockND, StandardNormal from dim 4; the default where no
+        fixed-dimension kernel exists, from dim 128 with fewer than 1024 chains)."""
         return int(L.lib().mmcmc_hmc_kernel_variant(self._h))
 
     def step(self) -> None:
