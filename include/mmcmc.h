@@ -44,7 +44,7 @@ extern "C" {
  *   mmcmc_hmc_group_set_step_size, mmcmc_hmc_group_set_n_leapfrog, mmcmc_mh_group_set_proposal_std,
  *   mmcmc_nuts_group_adapt_state, mmcmc_nuts_group_set_adapt_state, mmcmc_nuts_group_set_target_accept_p;
  *   rank-normalised diagnostics: mmcmc_rank_normalize, mmcmc_quantiles, mmcmc_rank_diagnostics;
- *   mmcmc_group_bind_collectives.
+ *   mmcmc_group_bind_collectives; the diagonal metric: mmcmc_{hmc,nuts}_set_metric, mmcmc_{hmc,nuts}_metric.
  * A binding checks mmcmc_version() >= the version it was generated from (rust/mini-mcmc-hip: assert_abi, in every constructor). */
 #define MMCMC_VERSION 102 /* 0.1.2 */
 
@@ -201,6 +201,32 @@ int mmcmc_hmc_set_state(mmcmc_hmc *h, const void *positions, int is_device, void
 int mmcmc_hmc_run_scheduled(mmcmc_hmc *h, size_t n_collect, size_t n_discard, const double *step_sizes,
                             const int32_t *n_leapfrogs, void *out, int out_is_device, uint64_t *accept_counts, void *stream);
 
+/* A diagonal mass matrix for HMC and NUTS (not in the reference, which integrates with the identity metric).  Additive as the
+ * setters above: MMCMC_VERSION stays 102; seed, chain offset, iteration counter and NUTS's adaptation records are untouched.
+ *   The metric is a scale per coordinate, scale[dim] (host doubles), each finite and > 0 -- also once converted to the
+ *     handle's element type (HMC) / tensor type (NUTS), which happens once, here.  It is M = diag(1 / s_i^2) written in whitened
+ *     momentum: the noise stream, the kinetic energy 1/2 sum p_i^2 and the accept rule stay as they are, and only the step
+ *     length becomes per-coordinate, e_i = eps * s_i (one multiplication in the element type), h_i = e_i / 2:
+ *       HMC:  first kick p_i = fma(h_i, g_i, p_i), drift x_i = fma(e_i, p_i, x_i), kick p_i = fma(last ? h_i : e_i, g_i, p_i);
+ *       NUTS: the leapfrog (the step-size search of init_chain goes through it) with e_i = +-eps * s_i, and the stop
+ *             criterion with diff_i = (x_plus_i - x_minus_i) * r_i, r_i = 1 / s_i in the tensor type; the summation order,
+ *             dual averaging, the slice variable and the tree bookkeeping are untouched.
+ *     With a metric of the target's posterior standard deviations a step size of order 1 is the natural scale.
+ *   A metric of all ones gives the bits of a handle without one.  NULL removes the metric.
+ *   It applies from the next transition on and to everything that advances the handle: step, run, run_rows, run_progress,
+ *     and run_scheduled (one launch per maximal run of equal pairs).
+ *   Every value is checked before anything changes: a non-finite or non-positive one returns MMCMC_ERR_INVALID_ARG.
+ *   Kernels: a handle with a metric runs a unit compiled at run time on the first set_metric of its (target kind, dimension)
+ *     -- seconds, once per process -- around the target's own functor (a built-in kind, or a kind registered from source:
+ *     plain, log-density alone, with data), verified bit for bit before the handle relies on it.  While a metric is set
+ *     the handle's kernel variant is 7 and set_kernel_variant to anything else returns MMCMC_ERR_UNSUPPORTED; after NULL the
+ *     handle has its previous variant again.  MMCMC_ERR_UNSUPPORTED, and nothing changed: a dimension above 32, no run-time
+ *     compiler on the machine, a unit that fails its check.  Device groups have no metric.
+ *   mmcmc_*_metric writes scale_out[dim] -- the doubles last set, ones when none is -- and returns 1 if a metric is set, 0 if
+ *     not, < 0 on error. */
+int mmcmc_hmc_set_metric(mmcmc_hmc *h, const double *scale); /* [dim], or NULL = identity */
+int mmcmc_hmc_metric(mmcmc_hmc *h, double *scale_out);
+
 /* ---- NUTS ------------------------------------------------------------------------------------------------
  * NUTS::new(target, initial_positions, target_accept_p)   nuts.rs:123-129 over NUTSChain::new nuts.rs:410-434.
  * init: host [n_chains, dim] doubles (the reference's Vec<Vec<T>>).  mode selects the reference's type split:
@@ -211,6 +237,10 @@ int mmcmc_hmc_run_scheduled(mmcmc_hmc *h, size_t n_collect, size_t n_discard, co
 typedef struct mmcmc_nuts mmcmc_nuts;
 int mmcmc_nuts_create(mmcmc_nuts **out, const mmcmc_target_desc *target, const double *init, size_t n_chains,
                       double target_accept_p, int mode, int device);
+/* the diagonal metric: see mmcmc_hmc_set_metric.  A search of the step size (epsilon = -1 in the adaptation records) that runs
+ * after the metric is set runs under it. */
+int mmcmc_nuts_set_metric(mmcmc_nuts *h, const double *scale); /* [dim], or NULL = identity */
+int mmcmc_nuts_metric(mmcmc_nuts *h, double *scale_out);
 /* NUTS::set_seed   nuts.rs:347-353 (keys the counter-based stream; chains differ by their global index) */
 int mmcmc_nuts_seed(mmcmc_nuts *h, uint64_t seed);
 int mmcmc_nuts_set_chain_offset(mmcmc_nuts *h, uint64_t chain_offset);

@@ -418,6 +418,30 @@ template <class T> class HMC {
         check(mmcmc_hmc_set_n_leapfrog(h_, n_leapfrog), "mmcmc_hmc_set_n_leapfrog");
         return *this;
     }
+    /* the diagonal metric (mmcmc_hmc_set_metric): a scale per coordinate, or clear_metric() for the identity */
+    HMC &set_metric(const std::vector<double> &scale)
+    {
+        if (scale.size() != dim_)
+            throw Error(MMCMC_ERR_SHAPE, "HMC::set_metric");
+        check(mmcmc_hmc_set_metric(h_, scale.data()), "mmcmc_hmc_set_metric");
+        return *this;
+    }
+    HMC &clear_metric()
+    {
+        check(mmcmc_hmc_set_metric(h_, nullptr), "mmcmc_hmc_set_metric");
+        return *this;
+    }
+    /* the scales last set, ones when none is; *is_set (may be NULL) tells which */
+    std::vector<double> metric(bool *is_set = nullptr)
+    {
+        std::vector<double> out(dim_);
+        const int st = mmcmc_hmc_metric(h_, out.data());
+        if (st < 0)
+            check(st, "mmcmc_hmc_metric");
+        if (is_set)
+            *is_set = st == 1;
+        return out;
+    }
     double step_size()
     {
         double eps = 0;
@@ -683,6 +707,29 @@ template <class T> class NUTS {
         check(mmcmc_nuts_set_adapt_state(h_, adapt.data()), "mmcmc_nuts_set_adapt_state");
         return *this;
     }
+    /* the diagonal metric (mmcmc_nuts_set_metric): a scale per coordinate, or clear_metric() for the identity */
+    NUTS &set_metric(const std::vector<double> &scale)
+    {
+        if (scale.size() != dim_)
+            throw Error(MMCMC_ERR_SHAPE, "NUTS::set_metric");
+        check(mmcmc_nuts_set_metric(h_, scale.data()), "mmcmc_nuts_set_metric");
+        return *this;
+    }
+    NUTS &clear_metric()
+    {
+        check(mmcmc_nuts_set_metric(h_, nullptr), "mmcmc_nuts_set_metric");
+        return *this;
+    }
+    std::vector<double> metric(bool *is_set = nullptr)
+    {
+        std::vector<double> out(dim_);
+        const int st = mmcmc_nuts_metric(h_, out.data());
+        if (st < 0)
+            check(st, "mmcmc_nuts_metric");
+        if (is_set)
+            *is_set = st == 1;
+        return out;
+    }
     StreamPosition stream_position()
     {
         StreamPosition p;
@@ -840,6 +887,29 @@ class NUTS64 {
             throw Error(MMCMC_ERR_SHAPE, "NUTS64::set_adapt_state");
         check(mmcmc_nuts_set_adapt_state(h_, adapt.data()), "mmcmc_nuts_set_adapt_state");
         return *this;
+    }
+    /* the diagonal metric (mmcmc_nuts_set_metric): a scale per coordinate, or clear_metric() for the identity */
+    NUTS64 &set_metric(const std::vector<double> &scale)
+    {
+        if (scale.size() != dim_)
+            throw Error(MMCMC_ERR_SHAPE, "NUTS64::set_metric");
+        check(mmcmc_nuts_set_metric(h_, scale.data()), "mmcmc_nuts_set_metric");
+        return *this;
+    }
+    NUTS64 &clear_metric()
+    {
+        check(mmcmc_nuts_set_metric(h_, nullptr), "mmcmc_nuts_set_metric");
+        return *this;
+    }
+    std::vector<double> metric(bool *is_set = nullptr)
+    {
+        std::vector<double> out(dim_);
+        const int st = mmcmc_nuts_metric(h_, out.data());
+        if (st < 0)
+            check(st, "mmcmc_nuts_metric");
+        if (is_set)
+            *is_set = st == 1;
+        return out;
     }
     StreamPosition stream_position()
     {

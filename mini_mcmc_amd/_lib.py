@@ -255,6 +255,11 @@ SIGNATURES = {
     "mmcmc_mh_group_set_iteration": (C.c_int, [_vp, C.c_uint64]),
     "mmcmc_nuts_group_stream_position": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mmcmc_nuts_group_set_iteration": (C.c_int, [_vp, C.c_uint64]),
+    # the diagonal metric of HMC and NUTS (include/mmcmc.h: "A diagonal mass matrix")
+    "mmcmc_hmc_set_metric": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_hmc_metric": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_nuts_set_metric": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_nuts_metric": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     # rank-normalised diagnostics (csrc/mm_rank.hip)
     "mmcmc_rank_normalize": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _vp, C.c_int, _vp,
                                        C.c_int, _vp]),

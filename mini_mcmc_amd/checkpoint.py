@@ -10,6 +10,9 @@ A checkpoint stores the target's KIND, not its parameters and not the data of a 
 data=)`): restoring onto a handle created over another array continues from the stored state under the new density, which is
 the caller's business.  Created over the same array, the handle continues bit for bit.
 
+A diagonal metric (`HMC.metric`, `NUTS.metric`) is part of a checkpoint: "metric", the scales as set, present only while one
+is set.  A checkpoint without the key -- every checkpoint written before metrics existed -- restores as "no metric".
+
 Not in a checkpoint: accept counts (per run), NUTS's cumulative leapfrog counts and depth histogram, tracker state
 (`MultiChainTracker`), the kernel variant and iters_per_launch (none of them changes a result).
 
@@ -155,6 +158,39 @@ def set_positions_host(obj, x) -> None:
         L.check(fn(obj._h, a.ctypes.data, 0, None), name)
 
 
+def get_metric(obj):
+    """The diagonal metric of an HMC / NUTS handle: its scales [dim] float64 as set, or None when none is set."""
+    out = np.empty(int(obj.dim), dtype=np.float64)
+    st = _fn(obj, "metric")(obj._h, out.ctypes.data_as(C.POINTER(C.c_double)))
+    if st < 0:
+        L.check(st, f"mmcmc_{obj._cprefix}_metric")
+    return out if st == 1 else None
+
+
+def check_metric(scale, dim: int) -> np.ndarray:
+    """[dim] float64, every value finite and > 0 (the library checks the handle's element type too)"""
+    a = np.ascontiguousarray(scale, dtype=np.float64)
+    if a.shape != (dim,):
+        raise ValueError(f"metric: shape {a.shape} != ({dim},)")
+    if not np.all(np.isfinite(a)) or not np.all(a > 0):
+        raise ValueError("metric: every scale must be finite and > 0")
+    return a
+
+
+def set_metric(obj, scale) -> None:
+    """scale [dim] (finite, > 0), or None for the identity; from the next transition on"""
+    name = f"mmcmc_{obj._cprefix}_set_metric"
+    if scale is None:
+        L.check(_fn(obj, "set_metric")(obj._h, None), name)
+        return
+    a = check_metric(scale, int(obj.dim))
+    L.check(_fn(obj, "set_metric")(obj._h, a.ctypes.data_as(C.POINTER(C.c_double))), name)
+
+
+def _has_metric(obj) -> bool:
+    return obj._ckpt_sampler in ("hmc", "nuts") and not _is_group(obj)
+
+
 def take(obj) -> dict:
     """The handle's (or group's) checkpoint: a dict of int / float / str scalars and numpy arrays."""
     dim, dt = _dims(obj)
@@ -166,6 +202,10 @@ def take(obj) -> dict:
     ck["positions"] = _positions(obj)
     if obj._ckpt_sampler == "nuts":
         ck["adapt"] = adapt_array(obj)
+    if _has_metric(obj):
+        m = get_metric(obj)
+        if m is not None:
+            ck["metric"] = m
     return ck
 
 
@@ -199,6 +239,11 @@ def apply(obj, ck: dict) -> None:
         if not (0 < tap < 1) or not 1 <= md <= _MAX_DEPTH:
             raise ValueError(f"checkpoint: target_accept_p {tap}, max_depth {md}")
         adapt = check_adapt(ck["adapt"], obj.n_chains, obj.mode)
+    metric = None
+    if "metric" in ck:
+        if not _has_metric(obj):
+            raise ValueError("checkpoint: it holds a metric, this handle cannot take one")
+        metric = check_metric(ck["metric"], dim)  # a wrong length is refused before anything is set
     pos = np.asarray(ck["positions"])
     shape = (obj.n_chains,) if s == "mh_discrete" else (obj.n_chains, dim)
     if pos.shape != shape or pos.dtype != np.dtype(dt):
@@ -218,6 +263,8 @@ def apply(obj, ck: dict) -> None:
     set_positions_host(obj, pos)
     if s == "nuts":
         set_adapt_array(obj, adapt)
+    if _has_metric(obj):
+        set_metric(obj, metric)  # None (a checkpoint without one): no metric
 
 
 def save(path, ckpt: dict) -> None:

@@ -178,6 +178,12 @@ struct Sampler {
     /* set for the duration of a scheduled run whose variant has a scheduled kernel: launch_range launches it */
     const void *sched_run = nullptr;
     uint32_t sched_iter0 = 0;
+    /* HMC's diagonal metric (mmcmc_hmc_set_metric): the scales as given (empty: none), their device image in the handle's
+     * element type [dim], the unit whose kernel reads it, and the variant to return to when the metric is cleared */
+    std::vector<double> metric;
+    void *d_metric = nullptr;
+    const mm_user_target *metric_unit = nullptr;
+    int variant_before_metric = MM_VAR_PAIRED;
 
     size_t esize() const { return dtype == MMCMC_F32 ? 4 : 8; }
 };
@@ -402,6 +408,8 @@ int sampler_destroy(Sampler *s)
         (void)hipFree(s->d_stage);
     if (s->d_sched)
         (void)hipFree(s->d_sched);
+    if (s->d_metric)
+        (void)hipFree(s->d_metric);
     if (s->ev_sched)
         (void)hipEventDestroy(s->ev_sched);
     (void)hipEventDestroy(s->ev0);
@@ -545,6 +553,15 @@ int launch_range(Sampler *s, const mm_kernel_entry<T> *k, const mm_tparams<T> &P
             e = mm_launch_hmc_lg(s->dim, q, stream);
         else
             e = mm_launch_hmc_lg32(s->dim, q, stream);
+        break;
+    }
+    case MM_LAUNCH_METRIC: {
+        /* the one-wave-per-SIMD skeleton around the target's functor with the metric, from the handle's metric unit */
+        mm_run_metric_args<T> m;
+        m.a = a;
+        m.metric = (const T *)s->d_metric;
+        e = mm_rtc_launch_run(s->metric_unit, 1, std::is_same<T, float>::value ? 0 : 1, &m, sizeof(m), grid, s->block,
+                              mm_tile_lds_bytes_rt(sizeof(T), s->dim), stream);
         break;
     }
     case MM_LAUNCH_SEGMENTED: /* sampler_run runs such a schedule as unscheduled launches: sched_run is never set for it */
@@ -796,6 +813,144 @@ int sampler_timing(Sampler *s, mmcmc_timing *t)
     MM_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     s->timing.kernel_ms = ms;
     *t = s->timing;
+    return MMCMC_OK;
+}
+
+/* The metric unit's HMC kernel is checked once per (unit, dtype) and process before a handle relies on it, on the handle's own
+ * parameter block (so a kind that carries data is checked on its data): up to 96 chains, 5 + 5 transitions with L = 3 from a
+ * fixed start, (a) with a general metric twice -- the same bits --, (b) with a metric of all ones against the handle's
+ * ordinary one-chain-per-lane kernel, which a ones-metric must reproduce bit for bit (mmcmc.h).  The handle's fields are
+ * borrowed for the launches and put back.  Only real verdicts are cached. */
+template <class T>
+bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tparams<T> &P, const mm_kernel_entry<T> *k)
+{
+    static std::mutex mu;
+    static std::map<std::pair<const void *, int>, bool> verdict;
+    const std::pair<const void *, int> key{(const void *)unit, s->dtype};
+    {
+        std::lock_guard<std::mutex> l(mu);
+        auto it = verdict.find(key);
+        if (it != verdict.end())
+            return it->second;
+    }
+    const size_t n = std::min<size_t>(96, s->n_chains), dim = (size_t)s->dim, nc = 5, nd = 5;
+    std::vector<T> x0(n * dim), ones(dim, T(1)), general(dim);
+    for (size_t c = 0; c < n; ++c)
+        for (size_t i = 0; i < dim; ++i)
+            x0[c * dim + i] = (T)(0.05 * (double)((int)((c * 7 + i * 13) % 17) - 8));
+    for (size_t i = 0; i < dim; ++i)
+        general[i] = (T)(0.75 + 0.125 * (double)(i % 5));
+    /* the handle's fields the launches read, borrowed and put back */
+    struct Borrow {
+        Sampler *s;
+        void *d_state, *d_metric;
+        size_t n_chains;
+        double scale;
+        int n_leapfrog, variant;
+        uint64_t seed, chain_offset, iter;
+        bool want_accept, metric;
+        const mm_user_target *unit;
+        const void *sched_run;
+        ~Borrow()
+        {
+            s->d_state = d_state, s->d_metric = d_metric, s->n_chains = n_chains, s->scale = scale, s->n_leapfrog = n_leapfrog;
+            s->variant = variant, s->seed = seed, s->chain_offset = chain_offset, s->iter = iter, s->want_accept = want_accept;
+            s->caps.metric = metric, s->metric_unit = unit, s->sched_run = sched_run;
+        }
+    } borrow{s, s->d_state, s->d_metric, s->n_chains, s->scale, s->n_leapfrog, s->variant, s->seed, s->chain_offset, s->iter,
+             s->want_accept, s->caps.metric, s->metric_unit, s->sched_run};
+    struct Dev {
+        T *x = nullptr, *out = nullptr, *met = nullptr;
+        ~Dev()
+        {
+            (void)hipFree(x);
+            (void)hipFree(out);
+            (void)hipFree(met);
+        }
+    } d;
+    if (hipMalloc((void **)&d.x, n * dim * sizeof(T)) != hipSuccess || hipMalloc((void **)&d.out, n * nc * dim * sizeof(T)) != hipSuccess ||
+        hipMalloc((void **)&d.met, dim * sizeof(T)) != hipSuccess)
+        return false;
+    s->d_state = d.x;
+    s->d_metric = d.met;
+    s->n_chains = n;
+    s->seed = 0x5eedull;
+    s->chain_offset = 0;
+    s->scale = 0.01; /* modest fixed scales, as builtin_unit_verified: the check is about the kernels */
+    s->n_leapfrog = 3;
+    s->want_accept = false;
+    s->sched_run = nullptr;
+    s->metric_unit = unit;
+    /* the one-chain-per-lane kernel the handle has without a metric: its unit, its fixed-dimension kernel, or run-time D */
+    const int plain = s->caps.unit != MM_UNIT_NONE ? MM_VAR_UNIT : s->caps.fixed ? (s->dim > 16 ? MM_VAR_PLAIN : MM_VAR_PAIRED) : MM_VAR_GENERIC;
+    /* metric == nullptr: the ordinary kernel */
+    auto one = [&](const std::vector<T> *metric, std::vector<T> &got) -> bool {
+        got.assign(n * nc * dim, T(0));
+        s->iter = 0;
+        s->caps.metric = metric != nullptr;
+        s->variant = metric ? MM_VAR_UNIT : plain;
+        return (!metric || hipMemcpy(d.met, metric->data(), dim * sizeof(T), hipMemcpyHostToDevice) == hipSuccess) &&
+               hipMemcpy(d.x, x0.data(), n * dim * sizeof(T), hipMemcpyHostToDevice) == hipSuccess &&
+               launch_range<T>(s, k, P, d.out, nc, (uint32_t)nd, (uint32_t)nc, 0, s->stream) == MMCMC_OK &&
+               hipStreamSynchronize(s->stream) == hipSuccess &&
+               hipMemcpy(got.data(), d.out, got.size() * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
+    };
+    std::vector<T> g1, g2, u1, p0;
+    if (!one(&general, g1) || !one(&general, g2) || !one(&ones, u1) || !one(nullptr, p0))
+        return false; /* an allocation or launch error: no verdict, the next set_metric tries again */
+    auto same = [](const std::vector<T> &a, const std::vector<T> &b) { return std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0; };
+    const bool ok = same(g1, g2) && same(u1, p0);
+    std::lock_guard<std::mutex> l(mu);
+    verdict[key] = ok;
+    return ok;
+}
+
+/* mmcmc_hmc_set_metric: every check before any change */
+int sampler_set_metric(Sampler *s, const double *scale)
+{
+    if (!scale) { /* the identity: back to the variant the handle had */
+        if (s->caps.metric) {
+            s->caps.metric = false;
+            s->variant = s->variant_before_metric;
+            s->metric.clear();
+        }
+        return MMCMC_OK;
+    }
+    const size_t dim = (size_t)s->dim;
+    for (size_t i = 0; i < dim; ++i) {
+        const double v = scale[i];
+        const double as_t = s->dtype == MMCMC_F32 ? (double)(float)v : v; /* finite and > 0 in the handle's element type too */
+        if (!std::isfinite(v) || !(v > 0.0) || !std::isfinite(as_t) || !(as_t > 0.0))
+            return MMCMC_ERR_INVALID_ARG;
+    }
+    if (mm_metric_status(s->caps) != MMCMC_OK)
+        return MMCMC_ERR_UNSUPPORTED;
+    DevGuard g(s->device);
+    const mm_user_target *unit = s->metric_unit;
+    if (!unit) {
+        /* a model's handle carries the model's kind, which has no gradient functor: mm_rtc_metric_unit answers NULL */
+        unit = mm_rtc_metric_unit(s->kind, s->dim);
+        if (!unit)
+            return MMCMC_ERR_UNSUPPORTED; /* no run-time compiler (or the unit does not build): nothing changed */
+    }
+    MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
+    if (!(s->dtype == MMCMC_F32 ? metric_unit_verified<float>(s, unit, s->Pf, s->kf) : metric_unit_verified<double>(s, unit, s->Pd, s->kd)))
+        return MMCMC_ERR_UNSUPPORTED;
+    if (!s->d_metric)
+        MM_HIP(hipMalloc(&s->d_metric, dim * s->esize()));
+    if (s->dtype == MMCMC_F32) {
+        std::vector<float> h(scale, scale + dim);
+        MM_HIP(hipMemcpy(s->d_metric, h.data(), dim * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+        MM_HIP(hipMemcpy(s->d_metric, scale, dim * sizeof(double), hipMemcpyHostToDevice));
+    }
+    s->metric_unit = unit;
+    s->metric.assign(scale, scale + dim);
+    if (!s->caps.metric) {
+        s->variant_before_metric = s->variant;
+        s->caps.metric = true;
+    }
+    s->variant = MM_VAR_UNIT;
     return MMCMC_OK;
 }
 
@@ -1232,6 +1387,16 @@ int mmcmc_hmc_params(mmcmc_hmc *h, double *step_size, int *n_leapfrog)
     if (n_leapfrog)
         *n_leapfrog = h->s->n_leapfrog;
     return MMCMC_OK;
+}
+int mmcmc_hmc_set_metric(mmcmc_hmc *h, const double *scale) { return h ? sampler_set_metric(h->s, scale) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_hmc_metric(mmcmc_hmc *h, double *scale_out)
+{
+    if (!h || !scale_out)
+        return MMCMC_ERR_INVALID_ARG;
+    const Sampler *s = h->s;
+    for (int i = 0; i < s->dim; ++i)
+        scale_out[i] = s->caps.metric ? s->metric[(size_t)i] : 1.0;
+    return s->caps.metric ? 1 : 0;
 }
 int mmcmc_hmc_set_state(mmcmc_hmc *h, const void *positions, int is_device, void *stream)
 {

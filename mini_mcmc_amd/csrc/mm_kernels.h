@@ -249,9 +249,10 @@ __device__ __forceinline__ void mm_flush_tile_raw(T *out, unsigned long long n_t
  * LCT > 0: compile-time leapfrog count (the loop is unrolled into that block).  Results are bit-identical for
  * every (PIPE, LCT): all variants evaluate the same functions (mm_rng.h, mm_samplers.h). */
 /* SCHED: HMC with PIPE = 2 only -- transition t takes (eps, L) from sched[t - sched_iter0] (mm_sched_at), run-time L */
-template <class T, class Tgt, int SAMPLER, int PIPE = 0, int LCT = 0, bool SCHED = false>
+/* Met: HMC's metric (mm_samplers.h); mm_no_metric for every kernel of the library, a mm_diag_metric in mm_run_metric_body */
+template <class T, class Tgt, int SAMPLER, int PIPE = 0, int LCT = 0, bool SCHED = false, class Met = mm_no_metric>
 __device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a, const mm_sched_step<T> *sched = nullptr,
-                                                   unsigned int sched_iter0 = 0)
+                                                   unsigned int sched_iter0 = 0, const Met &met = Met())
 {
     static_assert(!SCHED || (PIPE == 2 && LCT == 0 && SAMPLER == MM_SAMPLER_HMC), "scheduled runs: HMC, PIPE = 2, run-time L");
     constexpr int D = Tgt::dim;
@@ -303,7 +304,7 @@ __device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a, cons
             mm_draw_noise<D, Tab, MHP>(a.seed, chain, it + 1, zn, &un, tab);
             const T ln_un = mm_ln_accept(un, tab);
             if (SAMPLER == MM_SAMPLER_HMC)
-                acc = mm_hmc_step_noise<T, Tgt, LCT>(a.P, a.scale, a.n_leapfrog, x, &lp, g, zc, ln_uc);
+                acc = mm_hmc_step_noise<T, Tgt, LCT>(a.P, a.scale, a.n_leapfrog, x, &lp, g, zc, ln_uc, mm_no_hook(), nullptr, met);
             else
                 acc = mm_mh_step_noise<T, Tgt>(a.P, a.scale, x, &lp, zc, ln_uc);
             MM_UNROLL
@@ -311,7 +312,7 @@ __device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a, cons
                 zc[i] = zn[i];
             ln_uc = ln_un;
         } else if (SAMPLER == MM_SAMPLER_HMC) {
-            acc = mm_hmc_step<T, Tgt>(a.P, a.scale, a.n_leapfrog, x, &lp, g, a.seed, chain, it);
+            acc = mm_hmc_step<T, Tgt>(a.P, a.scale, a.n_leapfrog, x, &lp, g, a.seed, chain, it, met);
         } else {
             acc = mm_mh_step<T, Tgt>(a.P, a.scale, x, &lp, a.seed, chain, it);
         }
@@ -337,9 +338,9 @@ __device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a, cons
                 T eps;
                 int n_leapfrog;
                 mm_sched_at<T, SCHED>(a, sched, sched_iter0, iter_t, &eps, &n_leapfrog);
-                (void)mm_hmc_step_noise<T, Tgt, 0>(a.P, eps, n_leapfrog, x, &lp, g, z, ln_u, mm_no_hook(), &n_acc32);
+                (void)mm_hmc_step_noise<T, Tgt, 0>(a.P, eps, n_leapfrog, x, &lp, g, z, ln_u, mm_no_hook(), &n_acc32, met);
             } else if (SAMPLER == MM_SAMPLER_HMC)
-                (void)mm_hmc_step_noise<T, Tgt, LCT>(a.P, a.scale, a.n_leapfrog, x, &lp, g, z, ln_u, mm_no_hook(), &n_acc32);
+                (void)mm_hmc_step_noise<T, Tgt, LCT>(a.P, a.scale, a.n_leapfrog, x, &lp, g, z, ln_u, mm_no_hook(), &n_acc32, met);
             else
                 (void)mm_mh_step_noise<T, Tgt>(a.P, a.scale, x, &lp, z, ln_u, &n_acc32);
         };
@@ -451,6 +452,19 @@ template <class T, class Tgt, int SAMPLER, int PIPE = 0, int LCT = 0>
 __global__ __launch_bounds__(256) void mm_run_kernel(const mm_run_args<T> a)
 {
     mm_run_kernel_body<T, Tgt, SAMPLER, PIPE, LCT>(a);
+}
+
+/* HMC with a metric, in a run-time compiled unit only (mm_rtc.hip): mm_run_args followed by metric[D] = s_i in the element
+ * type, written by the host when the metric is set, read once per launch and the same for every lane */
+template <class T> struct mm_run_metric_args {
+    mm_run_args<T> a;
+    const T *metric;
+};
+template <class T, class Tgt, int PIPE> __device__ __forceinline__ void mm_run_metric_body(const mm_run_metric_args<T> &m)
+{
+    mm_diag_metric<T, Tgt::dim> met;
+    mm_metric_load<Tgt::dim>(m.metric, met.s); /* r is NUTS's: never read here */
+    mm_run_kernel_body<T, Tgt, MM_SAMPLER_HMC, PIPE, 0, false>(m.a, nullptr, 0u, met);
 }
 
 /* a scheduled run's kernel: the runtime-L PIPE = 2 instance reading (eps, L) per transition; sched is only read */

@@ -102,36 +102,41 @@ template <int D> MM_HD void mm_nuts_momentum(uint64_t seed, uint64_t chain, uint
 }
 
 /* nuts.rs:979-996, in place: (x, p, g) -> one leapfrog step of signed size eps; returns logp(x') */
-template <class TT, class Tgt> MM_HD TT mm_nuts_leapfrog(const mm_tparams<TT> &P, TT *x, TT *p, TT *g, TT eps)
+/* Met (mm_samplers.h): with a metric the step of coordinate i is e_i = eps * s_i and h_i = e_i / 2 */
+template <class TT, class Tgt, class Met = mm_no_metric>
+MM_HD TT mm_nuts_leapfrog(const mm_tparams<TT> &P, TT *x, TT *p, TT *g, TT eps, const Met &met = Met())
 {
     constexpr int D = Tgt::dim;
     const TT h = eps * TT(0.5);
     MM_UNROLL
     for (int i = 0; i < D; ++i) {
-        p[i] = mm_fma(h, g[i], p[i]);
-        x[i] = mm_fma(eps, p[i], x[i]);
+        p[i] = mm_fma(mm_half_step_at(met, eps, h, i), g[i], p[i]);
+        x[i] = mm_fma(mm_step_at(met, eps, i), p[i], x[i]);
     }
     TT lp = Tgt::logp_grad(P, x, g);
     MM_UNROLL
     for (int i = 0; i < D; ++i)
-        p[i] = mm_fma(h, g[i], p[i]);
+        p[i] = mm_fma(mm_half_step_at(met, eps, h, i), g[i], p[i]);
     return lp;
 }
 
 /* nuts.rs:963-977 */
-template <class TT, int D, class Red>
-MM_HD bool mm_stop_criterion(const TT *x_minus, const TT *x_plus, const TT *p_minus, const TT *p_plus)
+/* with a metric the momenta are whitened: the position difference is taken to the same coordinates, diff_i * r_i, r_i = 1 / s_i */
+template <class TT> MM_HD TT mm_whiten_at(const mm_no_metric &, TT d, int) { return d; }
+template <class TT, int D> MM_HD TT mm_whiten_at(const mm_diag_metric<TT, D> &m, TT d, int i) { return d * m.r[i]; }
+template <class TT, int D, class Red, class Met = mm_no_metric>
+MM_HD bool mm_stop_criterion(const TT *x_minus, const TT *x_plus, const TT *p_minus, const TT *p_plus, const Met &met = Met())
 {
     TT diff[D];
     MM_UNROLL
     for (int i = 0; i < D; ++i)
-        diff[i] = x_plus[i] - x_minus[i];
+        diff[i] = mm_whiten_at(met, x_plus[i] - x_minus[i], i);
     return Red::dot(diff, p_minus) >= TT(0) && Red::dot(diff, p_plus) >= TT(0);
 }
 
 /* nuts.rs:695-761 */
-template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>>
-MM_HD ST mm_find_reasonable_epsilon(const mm_tparams<TT> &P, const TT *position, const TT *mom)
+template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric>
+MM_HD ST mm_find_reasonable_epsilon(const mm_tparams<TT> &P, const TT *position, const TT *mom, const Met &met = Met())
 {
     constexpr int D = Tgt::dim;
     ST epsilon = 1;
@@ -146,7 +151,7 @@ MM_HD ST mm_find_reasonable_epsilon(const mm_tparams<TT> &P, const TT *position,
             p[i] = mom[i];
             g[i] = g0[i];
         }
-        return mm_nuts_leapfrog<TT, Tgt>(P, x, p, g, (TT)e);
+        return mm_nuts_leapfrog<TT, Tgt>(P, x, p, g, (TT)e, met);
     };
     TT ulogp_p = leap(epsilon);
     bool grad_real = true; /* grad_prime of the FIRST leapfrog only: the loop below never refreshes it (Q11) */
@@ -172,16 +177,16 @@ MM_HD ST mm_find_reasonable_epsilon(const mm_tparams<TT> &P, const TT *position,
 
 /* nuts.rs:528-545 init_chain, without the sample bookkeeping: always draws D normals (iteration 0 of the stream);
  * searches epsilon iff it is still the sentinel -1; mu = ln(10 epsilon). */
-template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>>
+template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric>
 MM_HD void mm_nuts_init_chain(const mm_tparams<TT> &P, const TT *position, mm_nuts_adapt<ST> *ad, ST eps_tol,
-                              uint64_t seed, uint64_t chain)
+                              uint64_t seed, uint64_t chain, const Met &met = Met())
 {
     constexpr int D = Tgt::dim;
     TT mom0[D];
     mm_nuts_momentum<D>(seed, chain, 0u, mom0);
     ST d = ad->epsilon + ST(1);
     if ((d < 0 ? -d : d) <= eps_tol)
-        ad->epsilon = mm_find_reasonable_epsilon<TT, ST, Tgt, Red>(P, position, mom0);
+        ad->epsilon = mm_find_reasonable_epsilon<TT, ST, Tgt, Red>(P, position, mom0, met);
     ad->mu = mm_logT(ST(10) * ad->epsilon);
 }
 
@@ -197,8 +202,12 @@ struct mm_nuts_info {
  * tick and lane, so that a lane whose tree is finished starts its next transition instead of idling.  Either way a
  * chain goes through exactly the same operations in the same order.
  * The outer edge in direction v is advanced on a copy (cx, cp, cg) and written back when the doubling ends. */
-template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>> struct mm_nuts_tree {
+/* Met (mm_samplers.h) is a base: the empty mm_no_metric adds nothing to the object; a mm_diag_metric is set once per chain
+ * (set_metric) and read by the leapfrog and by the stop criterion */
+template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric> struct mm_nuts_tree : Met {
     static constexpr int D = Tgt::dim;
+    MM_HD const Met &metric() const { return *this; }
+    MM_HD void set_metric(const Met &met) { static_cast<Met &>(*this) = met; }
     /* of the transition */
     TT xm[D], xp[D], pm[D], pp[D], gm[D], gp[D];
     ST joint, logu, alpha;
@@ -311,7 +320,7 @@ template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>> s
     /* one leaf: the leapfrog from the outer edge and the one-leaf subtree S it makes */
     MM_HD void leaf(const mm_tparams<TT> &P)
     {
-        const TT lp = mm_nuts_leapfrog<TT, Tgt>(P, cx, cp, cg, eps_signed);
+        const TT lp = mm_nuts_leapfrog<TT, Tgt>(P, cx, cp, cg, eps_signed, metric());
         info.n_leapfrog += 1;
         const ST jointp = (ST)(double)(lp - Red::dot(cp, cp) * TT(0.5));
         S_level = 0;
@@ -363,8 +372,8 @@ template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>> s
                     S_prime[i] = stk.v(e, 2, i);
             }
             S_n += n1;
-            const bool crit = (v == -1) ? mm_stop_criterion<TT, D, Red>(cx, fx, cp, fp)
-                                        : mm_stop_criterion<TT, D, Red>(fx, cx, fp, cp);
+            const bool crit = (v == -1) ? mm_stop_criterion<TT, D, Red>(cx, fx, cp, fp, metric())
+                                        : mm_stop_criterion<TT, D, Red>(fx, cx, fp, cp, metric());
             S_s = S_s && crit; /* the sibling's s' is 1, or it would not be waiting */
             S_alpha = stk.a(e) + S_alpha;
             S_nalpha += stk.c(e, 2);
@@ -433,8 +442,8 @@ template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>> s
             if (!take2)
                 S_prime[i] = L0_x[i];
         S_n += n1;
-        const bool crit = (v == -1) ? mm_stop_criterion<TT, D, Red>(cx, L0_x, cp, L0_p)
-                                    : mm_stop_criterion<TT, D, Red>(L0_x, cx, L0_p, cp);
+        const bool crit = (v == -1) ? mm_stop_criterion<TT, D, Red>(cx, L0_x, cp, L0_p, metric())
+                                    : mm_stop_criterion<TT, D, Red>(L0_x, cx, L0_p, cp, metric());
         S_s = S_s && crit;
         S_alpha = L0_alpha + S_alpha;
         S_nalpha += 1u;
@@ -512,7 +521,7 @@ template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>> s
                 x[i] = S_prime[i];
         }
         n += S_n;
-        s = S_s && mm_stop_criterion<TT, D, Red>(xm, xp, pm, pp);
+        s = S_s && mm_stop_criterion<TT, D, Red>(xm, xp, pm, pp, metric());
         j += 1;
         if (j >= max_depth)
             s = false; /* depth cap: not in the reference */
@@ -536,12 +545,13 @@ template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>> s
 };
 
 /* nuts.rs:550-691.  x[D] is updated in place; m is the 1-based global step count (self.m after the increment). */
-template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>>
+template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric>
 MM_HD mm_nuts_info mm_nuts_step(const mm_tparams<TT> &P, TT *x, mm_nuts_adapt<ST> *ad, uint32_t m, uint32_t n_discard,
                                 ST target_accept_p, int max_depth, uint64_t seed, uint64_t chain,
-                                const mm_nuts_stack<TT, ST, Tgt::dim> &stk)
+                                const mm_nuts_stack<TT, ST, Tgt::dim> &stk, const Met &met = Met())
 {
-    mm_nuts_tree<TT, ST, Tgt, Red> t;
+    mm_nuts_tree<TT, ST, Tgt, Red, Met> t;
+    t.set_metric(met);
     t.begin(P, x, m, seed, chain);
     while (t.s) {
         t.double_begin(*ad, seed, chain);
@@ -556,13 +566,14 @@ MM_HD mm_nuts_info mm_nuts_step(const mm_tparams<TT> &P, TT *x, mm_nuts_adapt<ST
 /* The same transition with the leaves taken in pairs (pair_first / pair_second / hand_up_free): the order in which
  * mm_nuts_pair_kernel walks a tree, run here back to back.  Bit-identical to mm_nuts_step by construction; the host
  * build compares the two (tests/test_nuts_parity_cpu.py). */
-template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>>
+template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric>
 MM_HD mm_nuts_info mm_nuts_step_pairs(const mm_tparams<TT> &P, TT *x, mm_nuts_adapt<ST> *ad, uint32_t m, uint32_t n_discard,
                                       ST target_accept_p, int max_depth, uint64_t seed, uint64_t chain,
-                                      const mm_nuts_stack<TT, ST, Tgt::dim> &stk)
+                                      const mm_nuts_stack<TT, ST, Tgt::dim> &stk, const Met &met = Met())
 {
-    using Tree = mm_nuts_tree<TT, ST, Tgt, Red>;
+    using Tree = mm_nuts_tree<TT, ST, Tgt, Red, Met>;
     Tree t;
+    t.set_metric(met);
     t.begin(P, x, m, seed, chain);
     auto draw = [&]() -> double { return t.aux(seed, chain); };
     while (t.s) {

@@ -41,6 +41,11 @@ struct NutsBase {
     virtual int leapfrog_counts(uint64_t *out) = 0;
     virtual int depth_histogram(uint32_t *out) = 0;
     virtual int set_variant(int v) = 0;
+    virtual int set_metric(const double *scale) = 0;
+    /* the diagonal metric (mmcmc_nuts_set_metric): the scales as given while one is set, and the variant to return to */
+    std::vector<double> metric;
+    bool has_metric = false;
+    int variant_before_metric = 0;
     int variant = 0; /* 0: one chain per lane, lanes in step; 4: one chain per lane, asynchronous lanes (default for
                       * dim <= 8); 1: lane-group / MFMA (mm_nuts_lg.h); 2: + tree-depth compaction, one
                         launch per level; 3: + compaction by a persistent scheduler */
@@ -77,6 +82,11 @@ template <class TT, class ST> struct Nuts : NutsBase {
     bool generic_ok = false;
     const mm_user_target *user = nullptr; /* run-time compiled target (mm_rtc.hip, variant 7) */
     size_t user_stack_bytes = 0, user_lds = 0;
+    /* with a metric: the unit whose kernels read it (mm_rtc_metric_unit), metric[2 dim] = s, then r = TT(1) / s, in the tensor type,
+     * and the stack area of its kernels (a handle on a compiled instance keeps its stack in LDS and has none of its own) */
+    const mm_user_target *metric_unit = nullptr;
+    TT *d_metric = nullptr;
+    unsigned char *d_metric_scratch = nullptr;
     TT *d_gstore = nullptr;
     int gstore_depth = 0;
     size_t g_pad = 0;
@@ -112,6 +122,8 @@ template <class TT, class ST> struct Nuts : NutsBase {
         (void)hipFree(d_hist);
         (void)hipFree(d_scratch);
         (void)hipFree(d_gstore);
+        (void)hipFree(d_metric);
+        (void)hipFree(d_metric_scratch);
         (void)hipFree(d_lg_scratch);
         (void)hipFree(d_lg_rec);
         (void)hipFree(d_lg_lists);
@@ -131,6 +143,196 @@ template <class TT, class ST> struct Nuts : NutsBase {
             (void)hipEventDestroy(ev1);
         if (stream)
             (void)hipStreamDestroy(stream);
+    }
+
+    /* mm_nuts_stack_layout<TT, ST, D>::bytes and the output tile of mm_tile<TT, D>, for a run-time D: what a unit's kernels
+     * take as stack area per wave and (lanes in step) as dynamic LDS */
+    static void unit_sizes(size_t D, size_t *stack_bytes, size_t *tile_lds)
+    {
+        const size_t a16 = 15;
+        *stack_bytes = (((size_t)MM_NUTS_JMAX * 3 * D * 64 * sizeof(TT) + a16) / 16 * 16) +
+                       (((size_t)MM_NUTS_JMAX * 64 * sizeof(ST) + a16) / 16 * 16) +
+                       (((size_t)MM_NUTS_JMAX * 3 * 64 * sizeof(uint32_t) + a16) / 16 * 16);
+        const int target = sizeof(TT) == 4 ? 96 : 48;
+        const int tile_t = (target / (int)D) >= 2 ? ((target / (int)D) & ~1) : 1;
+        const int run_len = tile_t * (int)D, epl = (int)(16 / sizeof(TT));
+        const int stride = (run_len % epl) == 0 ? run_len + epl : (run_len | 1);
+        *tile_lds = ((size_t)64 * stride * sizeof(TT) + 15) / 16 * 16; /* must mirror mm_kernels.h (mm_tile_default) */
+    }
+
+    static constexpr int type_mode_of = std::is_same<TT, double>::value ? 2 : (std::is_same<ST, double>::value ? 0 : 1);
+
+    /* the metric unit's kernels: init_chain, and a run by the pair kernel (which = 2: what handles launch) or with the lanes in
+     * step (which = 0: the second opinion of metric_unit_verified); `scratch` = the stack area, one unit_sizes() block per wave */
+    hipError_t metric_init(const mm_user_target *unit, const mm_nuts_init_args<TT, ST> &ia, const TT *met, hipStream_t st)
+    {
+        mm_nuts_init_metric_args<TT, ST> m;
+        m.a = ia;
+        m.metric = met;
+        return mm_rtc_launch_nuts(unit, type_mode_of, 1, &m, sizeof(m), (unsigned int)((ia.n_chains + 63) / 64), 0, st);
+    }
+    hipError_t metric_run(const mm_user_target *unit, const mm_nuts_args<TT, ST> &a, int which, const TT *met, hipStream_t st)
+    {
+        mm_nuts_metric_args<TT, ST> m;
+        m.a = a;
+        m.metric = met;
+        size_t stack = 0, tile = 0;
+        unit_sizes((size_t)dim, &stack, &tile);
+        return mm_rtc_launch_nuts(unit, type_mode_of, which, &m, sizeof(m), (unsigned int)((a.n_chains + 63) / 64),
+                                  which == 2 ? (size_t)MM_NUTS_RING * 64 * sizeof(double) : tile, st);
+    }
+
+    /* The metric unit is checked once per (unit, type mode) and process before a handle relies on it, like the units of
+     * rtc_unit_verified, on this handle's own parameter block (a kind that carries data is checked on its data): 96 chains,
+     * 5 + 5 transitions from a fixed start under a general metric, (a) twice by the pair kernel -- the same bits --, (b) by
+     * the unit's lanes-in-step kernel, which must agree bit for bit, under rtc_unit_verified's condition on the compiler
+     * that built the unit.  Only real verdicts are cached. */
+    bool metric_unit_verified(const mm_user_target *unit)
+    {
+        static std::mutex mu;
+        static std::map<const void *, bool> verdict;
+        {
+            std::lock_guard<std::mutex> l(mu);
+            auto it = verdict.find(unit);
+            if (it != verdict.end())
+                return it->second;
+        }
+        const size_t n = 96, D = (size_t)dim, nc = 5, nd = 5, waves = (n + 63) / 64;
+        size_t stack = 0, tile = 0;
+        unit_sizes(D, &stack, &tile);
+        std::vector<TT> x0(n * D), met(2 * D);
+        for (size_t c = 0; c < n; ++c)
+            for (size_t i = 0; i < D; ++i)
+                x0[c * D + i] = (TT)(0.05 * (double)((int)((c * 7 + i * 13) % 17) - 8));
+        for (size_t i = 0; i < D; ++i) {
+            met[i] = (TT)(0.75 + 0.125 * (double)(i % 5));
+            met[D + i] = TT(1) / met[i];
+        }
+        std::vector<mm_nuts_adapt<ST>> ad0(n);
+        for (auto &a : ad0) {
+            a.epsilon = (ST)-1;
+            a.epsilon_bar = (ST)1;
+            a.h_bar = (ST)0;
+            a.mu = (ST)std::log(10.0);
+        }
+        struct Dev {
+            TT *x = nullptr, *out = nullptr, *met = nullptr;
+            mm_nuts_adapt<ST> *ad = nullptr;
+            unsigned char *scratch = nullptr;
+            ~Dev()
+            {
+                (void)hipFree(x);
+                (void)hipFree(out);
+                (void)hipFree(met);
+                (void)hipFree(ad);
+                (void)hipFree(scratch);
+            }
+        } d;
+        if (hipMalloc((void **)&d.x, n * D * sizeof(TT)) != hipSuccess || hipMalloc((void **)&d.out, n * nc * D * sizeof(TT)) != hipSuccess ||
+            hipMalloc((void **)&d.met, 2 * D * sizeof(TT)) != hipSuccess || hipMalloc((void **)&d.ad, n * sizeof(mm_nuts_adapt<ST>)) != hipSuccess ||
+            hipMalloc((void **)&d.scratch, waves * stack) != hipSuccess ||
+            hipMemcpy(d.met, met.data(), 2 * D * sizeof(TT), hipMemcpyHostToDevice) != hipSuccess)
+            return false;
+        auto one = [&](int which, std::vector<TT> &got) -> bool {
+            got.assign(n * nc * D, TT(0));
+            if (hipMemcpy(d.x, x0.data(), n * D * sizeof(TT), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d.ad, ad0.data(), n * sizeof(mm_nuts_adapt<ST>), hipMemcpyHostToDevice) != hipSuccess)
+                return false;
+            mm_nuts_init_args<TT, ST> ia;
+            ia.P = P;
+            ia.state = d.x;
+            ia.adapt = d.ad;
+            ia.n_chains = n;
+            ia.seed = 0x5eedull;
+            ia.chain_offset = 0;
+            ia.eps_tol = sizeof(ST) == 4 ? (ST)1.1920929e-7 : (ST)2.220446049250313e-16;
+            mm_nuts_args<TT, ST> a;
+            a.P = P;
+            a.state = d.x;
+            a.adapt = d.ad;
+            a.out = d.out;
+            a.n_leapfrog = nullptr;
+            a.depth_hist = nullptr;
+            a.n_chains = n;
+            a.seed = ia.seed;
+            a.chain_offset = 0;
+            a.n_total = nc;
+            a.m0 = 0;
+            a.n_pre = (unsigned int)nd; /* run_progress' stepping: all ten transitions, the last five recorded */
+            a.n_rec = (unsigned int)nc;
+            a.write_initial = 0;
+            a.out_t0 = 0;
+            a.n_discard = (unsigned int)nd;
+            a.max_depth = 10;
+            a.target_accept_p = (ST)0.8;
+            a.stack_in_lds = 0;
+            a.async_batch = 0;
+            a.scratch = d.scratch;
+            return metric_init(unit, ia, d.met, stream) == hipSuccess && metric_run(unit, a, which, d.met, stream) == hipSuccess &&
+                   hipStreamSynchronize(stream) == hipSuccess &&
+                   hipMemcpy(got.data(), d.out, got.size() * sizeof(TT), hipMemcpyDeviceToHost) == hipSuccess;
+        };
+        std::vector<TT> a, a2, g;
+        if (!one(2, a) || !one(2, a2))
+            return false;
+        bool ok = std::memcmp(a.data(), a2.data(), a.size() * sizeof(TT)) == 0;
+        int process_hip = 0, built_hip = 0;
+        (void)mmcmc_rtc_compiler_info(nullptr, 0, &process_hip, &built_hip);
+        const bool referee_trusted = mm_rtc_compiler(unit) == MMCMC_RTC_COMPILER_HIPCC || (process_hip > 0 && process_hip / 100000 >= built_hip / 100000);
+        if (ok && referee_trusted) {
+            if (!one(0, g))
+                return false;
+            ok = std::memcmp(a.data(), g.data(), a.size() * sizeof(TT)) == 0;
+        }
+        std::lock_guard<std::mutex> l(mu);
+        verdict[unit] = ok;
+        return ok;
+    }
+
+    /* every value is checked before anything changes; NULL removes the metric and gives the handle its variant back */
+    int set_metric(const double *scale) override
+    {
+        if (!scale) {
+            if (has_metric) {
+                has_metric = false;
+                variant = variant_before_metric;
+                metric.clear();
+            }
+            return MMCMC_OK;
+        }
+        const size_t D = (size_t)dim;
+        std::vector<TT> h(2 * D);
+        for (size_t i = 0; i < D; ++i) {
+            h[i] = (TT)scale[i];
+            h[D + i] = TT(1) / h[i]; /* r_i, in the tensor type: what the stop criterion multiplies with */
+            if (!std::isfinite(scale[i]) || !(scale[i] > 0.0) || !std::isfinite(h[i]) || !(h[i] > TT(0)) || !std::isfinite(h[D + i]) || !(h[D + i] > TT(0)))
+                return MMCMC_ERR_INVALID_ARG;
+        }
+        if (dim > 32)
+            return MMCMC_ERR_UNSUPPORTED;
+        DevGuard g(device);
+        const mm_user_target *unit = metric_unit ? metric_unit : mm_rtc_metric_unit(kind, dim);
+        if (!unit)
+            return MMCMC_ERR_UNSUPPORTED; /* no run-time compiler (or the unit does not build): nothing changed */
+        MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
+        if (!metric_unit_verified(unit))
+            return MMCMC_ERR_UNSUPPORTED;
+        if (!d_metric)
+            MM_HIP(hipMalloc((void **)&d_metric, 2 * D * sizeof(TT)));
+        if (!d_metric_scratch) {
+            size_t stack = 0, tile = 0;
+            unit_sizes(D, &stack, &tile);
+            MM_HIP(hipMalloc((void **)&d_metric_scratch, (n_chains + 63) / 64 * stack));
+        }
+        MM_HIP(hipMemcpy(d_metric, h.data(), 2 * D * sizeof(TT), hipMemcpyHostToDevice));
+        metric_unit = unit;
+        metric.assign(scale, scale + D);
+        if (!has_metric) {
+            variant_before_metric = variant;
+            has_metric = true;
+        }
+        variant = 7;
+        return MMCMC_OK;
     }
 
     int setup(const mmcmc_target_desc *t, const double *init)
@@ -170,16 +372,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
                 if (!mm_rtc_nuts_usable(user, create_mode))
                     return MMCMC_ERR_UNSUPPORTED; /* this dimension and precision need more registers than a lane has */
             }
-            /* mm_nuts_stack_layout<TT, ST, D>::bytes and the output tile of mm_tile<TT, D>, for a run-time D */
-            const size_t D = (size_t)t->dim, a16 = 15;
-            user_stack_bytes = (((size_t)MM_NUTS_JMAX * 3 * D * 64 * sizeof(TT) + a16) / 16 * 16) +
-                               (((size_t)MM_NUTS_JMAX * 64 * sizeof(ST) + a16) / 16 * 16) +
-                               (((size_t)MM_NUTS_JMAX * 3 * 64 * sizeof(uint32_t) + a16) / 16 * 16);
-            const int target = sizeof(TT) == 4 ? 96 : 48;
-            const int tile_t = (target / (int)D) >= 2 ? ((target / (int)D) & ~1) : 1;
-            const int run_len = tile_t * (int)D, epl = (int)(16 / sizeof(TT));
-            const int stride = (run_len % epl) == 0 ? run_len + epl : (run_len | 1);
-            user_lds = ((size_t)64 * stride * sizeof(TT) + 15) / 16 * 16; /* must mirror mm_kernels.h (mm_tile_default) */
+            unit_sizes((size_t)t->dim, &user_stack_bytes, &user_lds);
         } else if (!k && !generic_ok) {
             return MMCMC_ERR_UNSUPPORTED;
         }
@@ -272,6 +465,8 @@ template <class TT, class ST> struct Nuts : NutsBase {
 
     int set_variant(int v) override
     {
+        if (has_metric) /* only the metric unit has kernels that read a metric: it is variant 7 until the metric is cleared */
+            return v == 7 ? MMCMC_OK : (v >= 0 && v <= 7) ? MMCMC_ERR_UNSUPPORTED : MMCMC_ERR_INVALID_ARG;
         if ((v == 0 && k) || (v >= 1 && v <= 3 && lg) || (v == 4 && k && k->run_async) || (v == 5 && k && k->run_pair) ||
             (v == 6 && generic_ok) || (v == 7 && user)) {
             variant = v;
@@ -576,7 +771,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
         const int type_mode = std::is_same<TT, double>::value ? 2 : (std::is_same<ST, double>::value ? 0 : 1);
         const unsigned int grid64 = (unsigned int)((n_chains + 63) / 64);
         hipError_t e;
-        const bool rtc_target = user && variant == 7; /* kernels of a run-time compiled unit */
+        const bool rtc_target = (user && variant == 7) || has_metric; /* kernels of a run-time compiled unit */
         if (rtc_target) {
             mm_nuts_init_args<TT, ST> ia;
             ia.P = P;
@@ -586,7 +781,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
             ia.seed = seed;
             ia.chain_offset = chain_offset;
             ia.eps_tol = sizeof(ST) == 4 ? (ST)1.1920929e-7 : (ST)2.220446049250313e-16;
-            e = mm_rtc_launch_nuts(user, type_mode, 1, &ia, sizeof(ia), grid64, 0, st);
+            e = has_metric ? metric_init(metric_unit, ia, d_metric, st) : mm_rtc_launch_nuts(user, type_mode, 1, &ia, sizeof(ia), grid64, 0, st);
         } else {
             e = use_lg ? init_lg(st) : use_generic ? launch_generic(ga, 1, st) : k->init(P, d_state, d_adapt, n_chains, seed, chain_offset, st);
         }
@@ -638,7 +833,12 @@ template <class TT, class ST> struct Nuts : NutsBase {
         }
         MM_HIP(hipEventRecord(ev0, st));
         const unsigned int a_pre = a.n_pre, a_rec = a.n_rec;
-        if (rtc_target) {
+        if (has_metric) {
+            /* the metric unit's pair kernel, its stack in the handle's metric scratch area */
+            a.scratch = d_metric_scratch;
+            a.stack_in_lds = 0;
+            e = metric_run(metric_unit, a, 2, d_metric, st);
+        } else if (rtc_target) {
             /* a run-time compiled target: asynchronous lanes with the leaves in pairs (mm_nuts_pair_body; dynamic LDS = the
              * ring of uniforms, stack in the scratch area).  The unit's lanes-in-step kernel (mm_nuts_run_body) is NOT
              * launched: it gave wrong, run-to-run different samples at RosenbrockND(19) / (23) in f64 and a memory fault at
@@ -973,6 +1173,15 @@ int mmcmc_nuts_state(mmcmc_nuts *h, void *out) { return (h && out) ? h->p->state
 int mmcmc_nuts_adapt_state(mmcmc_nuts *h, double *out)
 {
     return (h && out) ? h->p->adapt_state(out) : MMCMC_ERR_INVALID_ARG;
+}
+int mmcmc_nuts_set_metric(mmcmc_nuts *h, const double *scale) { return h ? h->p->set_metric(scale) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_nuts_metric(mmcmc_nuts *h, double *scale_out)
+{
+    if (!h || !scale_out)
+        return MMCMC_ERR_INVALID_ARG;
+    for (int i = 0; i < h->p->dim; ++i)
+        scale_out[i] = h->p->has_metric ? h->p->metric[(size_t)i] : 1.0;
+    return h->p->has_metric ? 1 : 0;
 }
 int mmcmc_nuts_set_state(mmcmc_nuts *h, const void *x, int is_device, void *stream)
 {

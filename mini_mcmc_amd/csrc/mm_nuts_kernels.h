@@ -77,10 +77,10 @@ template <class TT, class ST> struct mm_nuts_init_args { /* the same as one bloc
     unsigned long long n_chains, seed, chain_offset;
     ST eps_tol;
 };
-template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>>
+template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric>
 __device__ __forceinline__ void mm_nuts_init_body(const mm_tparams<TT> &P, const TT *state, mm_nuts_adapt<ST> *adapt,
                                                   unsigned long long n_chains, unsigned long long seed,
-                                                  unsigned long long chain_offset, ST eps_tol)
+                                                  unsigned long long chain_offset, ST eps_tol, const Met &met = Met())
 {
     constexpr int D = Tgt::dim;
     const unsigned long long c = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -91,7 +91,7 @@ __device__ __forceinline__ void mm_nuts_init_body(const mm_tparams<TT> &P, const
     for (int i = 0; i < D; ++i)
         x[i] = state[c * D + i];
     mm_nuts_adapt<ST> ad = adapt[c];
-    mm_nuts_init_chain<TT, ST, Tgt, Red>(P, x, &ad, eps_tol, seed, chain_offset + c);
+    mm_nuts_init_chain<TT, ST, Tgt, Red>(P, x, &ad, eps_tol, seed, chain_offset + c, met);
     adapt[c] = ad;
 }
 template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>>
@@ -104,8 +104,8 @@ __global__ void mm_nuts_init_kernel(const mm_tparams<TT> P, const TT *state, mm_
 
 /* LDS_STACK is a template parameter, not a run-time choice: a pointer that may be LDS or HBM is a generic pointer and
  * every stack access a flat_load / flat_store (which is what these kernels did at first, stack "in LDS" included). */
-template <class TT, class ST, class Tgt, bool LDS_STACK>
-__device__ __forceinline__ void mm_nuts_run_body(const mm_nuts_args<TT, ST> &a)
+template <class TT, class ST, class Tgt, bool LDS_STACK, class Met = mm_no_metric>
+__device__ __forceinline__ void mm_nuts_run_body(const mm_nuts_args<TT, ST> &a, const Met &met = Met())
 {
     constexpr int D = Tgt::dim;
     using Tile = mm_tile<TT, D>;
@@ -169,7 +169,7 @@ __device__ __forceinline__ void mm_nuts_run_body(const mm_nuts_args<TT, ST> &a)
         /* inactive lanes take no transition: an arbitrary state could grow an arbitrarily deep tree */
         if (active) {
             const mm_nuts_info inf = mm_nuts_step<TT, ST, Tgt>(a.P, x, &ad, m, a.n_discard, a.target_accept_p,
-                                                               a.max_depth, a.seed, chain, stk);
+                                                               a.max_depth, a.seed, chain, stk, met);
             n_lf += inf.n_leapfrog;
             if (a.depth_hist)
                 atomicAdd(&hist_lds[inf.depth < MM_NUTS_JMAX ? inf.depth : MM_NUTS_JMAX], 1u);
@@ -360,12 +360,12 @@ __global__ __launch_bounds__(64) void mm_nuts_async_kernel(const mm_nuts_args<TT
 #endif
 /* the kernel proper is a device function so that a run-time compiled unit (csrc/mm_rtc.hip: user targets, built-in targets
  * at dimensions without a compiled instance) can wrap it in an extern "C" kernel of its own, like mm_nuts_run_body */
-template <class TT, class ST, class Tgt, bool LDS_STACK>
-__device__ __forceinline__ void mm_nuts_pair_body(const mm_nuts_args<TT, ST> &a)
+template <class TT, class ST, class Tgt, bool LDS_STACK, class Met = mm_no_metric>
+__device__ __forceinline__ void mm_nuts_pair_body(const mm_nuts_args<TT, ST> &a, const Met &met = Met())
 {
     constexpr int D = Tgt::dim;
     using Lay = mm_nuts_stack_layout<TT, ST, D>;
-    using Tree = mm_nuts_tree<TT, ST, Tgt>;
+    using Tree = mm_nuts_tree<TT, ST, Tgt, mm_red_seq<TT, D>, Met>;
     extern __shared__ __attribute__((aligned(16))) unsigned char mm_lds_raw[];
     const int lane = threadIdx.x & 63;
     __shared__ unsigned int hist_lds[MM_NUTS_JMAX + 1]; /* see mm_nuts_run_kernel */
@@ -403,6 +403,7 @@ __device__ __forceinline__ void mm_nuts_pair_body(const mm_nuts_args<TT, ST> &a)
     const unsigned int first = a.write_initial ? 1u : 0u;
 
     Tree T;
+    T.set_metric(met);
     unsigned long long n_lf = 0;
     unsigned int m = a.m0, done = 0;
     unsigned int aux_p = 0; /* uniforms of transition T.m produced so far (even); T.aux_k: consumed */
@@ -550,6 +551,39 @@ template <class TT, class ST, class Tgt, bool LDS_STACK>
 __global__ __launch_bounds__(64) void mm_nuts_pair_kernel(const mm_nuts_args<TT, ST> a)
 {
     mm_nuts_pair_body<TT, ST, Tgt, LDS_STACK>(a);
+}
+
+/* The kernels of a handle with a metric (mm_samplers.h: mm_diag_metric), in a run-time compiled unit only (mm_rtc.hip): the
+ * existing argument blocks followed by metric[2 D] = s_0 .. s_{D-1}, r_0 .. r_{D-1} with r_i = TT(1) / s_i, in the tensor type,
+ * written by the host when the metric is set and read once per launch, the same values for every lane. */
+template <class TT, class ST> struct mm_nuts_init_metric_args {
+    mm_nuts_init_args<TT, ST> a;
+    const TT *metric;
+};
+template <class TT, class ST> struct mm_nuts_metric_args {
+    mm_nuts_args<TT, ST> a;
+    const TT *metric;
+};
+template <class TT, int D> __device__ __forceinline__ mm_diag_metric<TT, D> mm_nuts_metric_of(const TT *metric)
+{
+    mm_diag_metric<TT, D> met;
+    mm_metric_load<D>(metric, met.s);
+    mm_metric_load<D>(metric + D, met.r);
+    return met;
+}
+template <class TT, class ST, class Tgt>
+__device__ __forceinline__ void mm_nuts_init_metric_body(const mm_nuts_init_metric_args<TT, ST> &m)
+{
+    mm_nuts_init_body<TT, ST, Tgt>(m.a.P, m.a.state, m.a.adapt, m.a.n_chains, m.a.seed, m.a.chain_offset, m.a.eps_tol,
+                                   mm_nuts_metric_of<TT, Tgt::dim>(m.metric));
+}
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_run_metric_body(const mm_nuts_metric_args<TT, ST> &m)
+{
+    mm_nuts_run_body<TT, ST, Tgt, false>(m.a, mm_nuts_metric_of<TT, Tgt::dim>(m.metric));
+}
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_pair_metric_body(const mm_nuts_metric_args<TT, ST> &m)
+{
+    mm_nuts_pair_body<TT, ST, Tgt, false>(m.a, mm_nuts_metric_of<TT, Tgt::dim>(m.metric));
 }
 
 #if !defined(__HIPCC_RTC__) /* host side: not part of the run-time compiled kernels of user targets (mm_rtc.hip) */

@@ -46,6 +46,8 @@ struct mm_path_caps {
     bool wide_ok = false;
     bool lg_ok = false;
     bool few_chains = false;  /* dim >= 128 && n_chains < 1024: where the wide kernel is the default */
+    bool metric = false;      /* HMC: a diagonal metric is set (mmcmc_hmc_set_metric): the handle runs its metric unit, variant 7,
+                                 whatever it ran before; cleared again with the metric */
 };
 
 /* one enumerator per launcher launch_range can call */
@@ -61,7 +63,8 @@ enum mm_launch {
     MM_LAUNCH_GENERIC,     /* mm_launch_run_generic_* */
     MM_LAUNCH_WIDE,        /* mm_launch_hmc_wide_* */
     MM_LAUNCH_LG,          /* mm_launch_hmc_lg / mm_launch_hmc_lg32 */
-    MM_LAUNCH_SEGMENTED    /* a scheduled run without a scheduled kernel: one unscheduled launch per run of equal (eps, L) */
+    MM_LAUNCH_SEGMENTED,   /* a scheduled run without a scheduled kernel: one unscheduled launch per run of equal (eps, L) */
+    MM_LAUNCH_METRIC       /* the HMC kernel of the handle's metric unit (mm_rtc_metric_unit): mm_rtc_launch_run with mm_run_metric_args */
 };
 
 /* no fixed-dimension kernel and not a caller's unit: the run-time-dimension kernel is what the handle falls back on */
@@ -89,7 +92,16 @@ static inline bool mm_path_caps_consistent(const mm_path_caps &c)
         return false; /* GaussianND has fixed entries at 16 and 32 */
     if (c.few_chains && c.dim < 128)
         return false;
+    if (c.metric && (!hmc || c.dim > 32))
+        return false; /* mm_metric_status refused it */
     return true;
+}
+
+/* may a handle take a metric?  HMC up to dim 32, whatever mapping it runs now (lane groups and the wide kernel have no
+ * metric form: the handle moves to its metric unit); the run-time compiler is asked for afterwards */
+static inline int mm_metric_status(const mm_path_caps &c)
+{
+    return c.sampler == MM_SAMPLER_HMC && c.dim >= 1 && c.dim <= 32 ? MMCMC_OK : MMCMC_ERR_UNSUPPORTED;
 }
 
 static inline int mm_default_variant(const mm_path_caps &c)
@@ -116,6 +128,8 @@ static inline int mm_variant_status(const mm_path_caps &c, int variant)
         return MMCMC_ERR_INVALID_ARG;
     if (c.sampler == MM_SAMPLER_MH && (variant == MM_VAR_LG || variant == MM_VAR_WIDE))
         return MMCMC_ERR_INVALID_ARG;
+    if (c.metric) /* only the metric unit has kernels that read a metric */
+        return variant == MM_VAR_UNIT ? MMCMC_OK : MMCMC_ERR_UNSUPPORTED;
     if (c.unit == MM_UNIT_BUILTIN) /* its run-time compiled register kernels, or the run-time-dimension kernel they are checked against */
         return variant == MM_VAR_GENERIC || variant == MM_VAR_UNIT ? MMCMC_OK : MMCMC_ERR_UNSUPPORTED;
     if (c.unit == MM_UNIT_CALLER)
@@ -141,6 +155,8 @@ static inline int mm_variant_status(const mm_path_caps &c, int variant)
 static inline mm_launch mm_launch_path(const mm_path_caps &c, int variant, int n_leapfrog, bool scheduled)
 {
     const bool hmc = c.sampler == MM_SAMPLER_HMC, l10 = hmc && n_leapfrog == 10;
+    if (c.metric) /* one kernel, run-time L; a schedule goes through the segmented fallback */
+        return scheduled ? MM_LAUNCH_SEGMENTED : MM_LAUNCH_METRIC;
     if (scheduled) {
         /* kernels that read the schedule on the device: the split kernel and PIPE = 2 of the fixed-dimension targets */
         if (hmc && c.fixed && variant == MM_VAR_SPLIT && c.split_sched)

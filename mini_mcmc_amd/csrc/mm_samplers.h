@@ -235,6 +235,42 @@ MM_HD int mm_mh_step(const mm_tparams<T> &P, T prop_std, T *x, T *lp, uint64_t s
     return mm_mh_step_noise<T, Tgt>(P, prop_std, x, lp, z, mm_ln_accept(u, mm_icdf_global()));
 }
 
+/* The metric of HMC and NUTS: nothing (the identity: one step length for every coordinate), or a scale s[D] > 0 per
+ * coordinate -- M = diag(1 / s_i^2), written in whitened momentum, so that only the step length becomes per-coordinate:
+ * e_i = eps * s_i.  r[D] = 1 / s_i is what NUTS's stop criterion multiplies a position difference with (mm_nuts.h); HMC
+ * never reads it.  The same s (and r) serve every chain: a kernel reads them once, through mm_metric_load. */
+struct mm_no_metric {
+    static constexpr bool on = false;
+};
+template <class T, int D> struct mm_diag_metric {
+    static constexpr bool on = true;
+    T s[D], r[D];
+};
+/* the step length of coordinate i and half of it; `h` = eps / 2 as the caller already holds it */
+template <class T> MM_HD T mm_step_at(const mm_no_metric &, T eps, int) { return eps; }
+template <class T> MM_HD T mm_half_step_at(const mm_no_metric &, T, T h, int) { return h; }
+template <class T, int D> MM_HD T mm_step_at(const mm_diag_metric<T, D> &m, T eps, int i) { return eps * m.s[i]; }
+template <class T, int D> MM_HD T mm_half_step_at(const mm_diag_metric<T, D> &m, T eps, T, int i) { return (eps * m.s[i]) * T(0.5); }
+/* a kick between two leapfrog steps: `k` = last ? h : eps as the caller already holds it */
+template <class T> MM_HD T mm_kick_at(const mm_no_metric &, T, T k, bool, int) { return k; }
+template <class T, int D> MM_HD T mm_kick_at(const mm_diag_metric<T, D> &m, T eps, T, bool last, int i)
+{
+    return last ? (eps * m.s[i]) * T(0.5) : eps * m.s[i];
+}
+/* out[i] = base[i], i < D, of an array that is written by the host only and the same for every lane: on the device through
+ * the constant address space, as mm_data_row reads a row (mm_data.h) -- scalar loads, no per-lane copy */
+template <int D, class T> MM_HD void mm_metric_load(const T *__restrict__ base, T (&out)[D])
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const T __attribute__((address_space(4))) *p = (const T __attribute__((address_space(4))) *)base;
+#else
+    const T *p = base;
+#endif
+    MM_UNROLL
+    for (int i = 0; i < D; ++i)
+        out[i] = p[i];
+}
+
 /* One HMC transition given its noise: p[D] ~ N(0,1) (momentum; clobbered) and ln_u.  x[D], lp = logp(x),
  * g = grad logp(x) are updated in place; returns 1 on accept. */
 struct mm_no_hook {
@@ -244,9 +280,12 @@ struct mm_no_hook {
 /* Hook: called after leapfrog step l = 0, 1, ... with independent work to be issued alongside the integrator's
  * dependent chain; it must not touch the transition's data.  The kernels pass mm_no_hook (nothing): threading the next
  * iterations' Philox rounds through here was measured (tools/hmc_split.hip) and is slower, DESIGN.md 5.1. */
-template <class T, class Tgt, int LCT = 0, class Red = mm_red_seq<T, Tgt::dim>, class Hook = mm_no_hook>
+/* Met: the metric (above).  mm_no_metric: the scalar eps for every coordinate, the expressions below as they always were.
+ * mm_diag_metric: e_i = eps * s_i (one multiplication in T), h_i = e_i / 2 in their place; noise, kinetic energy and accept
+ * rule are the same -- HMC with M = diag(1 / s_i^2) in whitened momentum. */
+template <class T, class Tgt, int LCT = 0, class Red = mm_red_seq<T, Tgt::dim>, class Hook = mm_no_hook, class Met = mm_no_metric>
 MM_HD int mm_hmc_step_noise(const mm_tparams<T> &P, T eps, int n_leapfrog, T *x, T *lp, T *g, T *p, T ln_u,
-                            Hook &&hook = Hook(), unsigned int *n_accepted = nullptr)
+                            Hook &&hook = Hook(), unsigned int *n_accepted = nullptr, const Met &met = Met())
 {
     /* Red: summation order of the two kinetic-energy dot products (mm_targets.h): sequential for one chain per lane,
      * grouped for the lane-group kernel (mm_hmc_lg.h), whose bit-exact host twin this then is */
@@ -269,17 +308,17 @@ MM_HD int mm_hmc_step_noise(const mm_tparams<T> &P, T eps, int n_leapfrog, T *x,
     auto leap = [&](bool last) {
         MM_UNROLL
         for (int i = 0; i < D; ++i)
-            xn[i] = mm_fma(eps, p[i], xn[i]); /* drift */
+            xn[i] = mm_fma(mm_step_at(met, eps, i), p[i], xn[i]); /* drift */
         lpn = Tgt::logp_grad(P, xn, gn);
         const T k = last ? h : eps;
         MM_UNROLL
         for (int i = 0; i < D; ++i)
-            p[i] = mm_fma(k, gn[i], p[i]);
+            p[i] = mm_fma(mm_kick_at(met, eps, k, last, i), gn[i], p[i]);
     };
     if constexpr (LCT > 0) {
         MM_UNROLL
         for (int i = 0; i < D; ++i)
-            p[i] = mm_fma(h, gn[i], p[i]); /* first half kick, with the gradient of the current position */
+            p[i] = mm_fma(mm_half_step_at(met, eps, h, i), gn[i], p[i]); /* first half kick, with the gradient of the current position */
         MM_UNROLL
         for (int l = 0; l < LCT; ++l) {
             leap(l + 1 == LCT);
@@ -288,7 +327,7 @@ MM_HD int mm_hmc_step_noise(const mm_tparams<T> &P, T eps, int n_leapfrog, T *x,
     } else if (n_leapfrog > 0) {
         MM_UNROLL
         for (int i = 0; i < D; ++i)
-            p[i] = mm_fma(h, gn[i], p[i]);
+            p[i] = mm_fma(mm_half_step_at(met, eps, h, i), gn[i], p[i]);
         for (int l = 0; l < n_leapfrog; ++l) {
             leap(l + 1 == n_leapfrog);
             hook(l);
@@ -311,14 +350,14 @@ MM_HD int mm_hmc_step_noise(const mm_tparams<T> &P, T eps, int n_leapfrog, T *x,
     return acc;
 }
 
-template <class T, class Tgt>
+template <class T, class Tgt, class Met = mm_no_metric>
 MM_HD int mm_hmc_step(const mm_tparams<T> &P, T eps, int n_leapfrog, T *x, T *lp, T *g, uint64_t seed,
-                      uint64_t chain, uint32_t iter)
+                      uint64_t chain, uint32_t iter, const Met &met = Met())
 {
     constexpr int D = Tgt::dim;
     T p[D], u;
     mm_draw_noise<D>(seed, chain, iter, p, &u);
-    return mm_hmc_step_noise<T, Tgt>(P, eps, n_leapfrog, x, lp, g, p, mm_ln_accept(u, mm_icdf_global()));
+    return mm_hmc_step_noise<T, Tgt>(P, eps, n_leapfrog, x, lp, g, p, mm_ln_accept(u, mm_icdf_global()), mm_no_hook(), nullptr, met);
 }
 
 #endif /* MM_SAMPLERS_H */

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import checkpoint as K
 from .core import _Sampler
 from .distributions import IsotropicGaussian, Target
 
@@ -86,6 +87,19 @@ class HMC(_Sampler):
     @n_leapfrog.setter
     def n_leapfrog(self, n: int) -> None:
         L.check(L.lib().mmcmc_hmc_set_n_leapfrog(self._h, int(n)), "mmcmc_hmc_set_n_leapfrog")
+
+    @property
+    def metric(self):
+        """The diagonal metric: scales [dim] float64 (M = diag(1 / s_i^2); the step of coordinate i is step_size * s_i), or
+        None when none is set.  Setting it (an array of finite scales > 0, or None to clear) applies from the next transition
+        on, to step / run / run_progress / run_scheduled alike; a metric of ones gives the bits of no metric.  With the
+        posterior's standard deviations as scales a step_size of order 1 is the natural scale (warmup.warmup_hmc).  Up to
+        dim 32; the first use compiles the target's metric unit (seconds); kernel_variant is 7 while a metric is set."""
+        return K.get_metric(self)
+
+    @metric.setter
+    def metric(self, scale) -> None:
+        K.set_metric(self, scale)
 
     @property
     def positions(self) -> np.ndarray:

@@ -140,6 +140,19 @@ class NUTS(K.Checkpointable):
         K.set_adapt_array(self, adapt)
         return self
 
+    @property
+    def metric(self):
+        """The diagonal metric: scales [dim] float64 (M = diag(1 / s_i^2); the leapfrog steps coordinate i by epsilon * s_i), or
+        None when none is set.  Setting it (finite scales > 0, or None to clear) applies from the next run on; seed, iteration
+        and adaptation records are untouched -- set epsilon to the sentinel -1 (set_adapt_state) to have the next run search
+        the step size under the new metric, as warmup.warmup_nuts does.  Up to dim 32; the first use compiles the target's
+        metric unit (seconds); kernel_variant is 7 while a metric is set."""
+        return K.get_metric(self)
+
+    @metric.setter
+    def metric(self, scale) -> None:
+        K.set_metric(self, scale)
+
     def _params(self):
         p, d = C.c_double(), C.c_int()
         L.check(L.lib().mmcmc_nuts_params(self._h, C.byref(p), C.byref(d)), "mmcmc_nuts_params")
