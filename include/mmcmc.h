@@ -233,7 +233,12 @@ int mmcmc_hmc_metric(mmcmc_hmc *h, double *scale_out);
  *   0 = f32 tensors + f64 scalars  (`NUTS<f64, Autodiff<NdArray>, _>`: NdArray elements are f32)
  *   1 = f32 tensors + f32 scalars  (`NUTS<f32, Autodiff<NdArray>, _>`)
  *   2 = f64 tensors + f64 scalars  (BASELINE.json config 5 "f64"; no default reference backend has f64 elements)
- * Samples are of the tensor type (f32 for modes 0/1, f64 for mode 2). */
+ * Samples are of the tensor type (f32 for modes 0/1, f64 for mode 2).
+ * Any bits are accepted as a start, here and by mmcmc_nuts_set_state.  A chain whose start has no real log-density in the
+ *   tensor type -- a NaN or infinite coordinate, or a finite one where the density overflows -- does not move: the step-size
+ *   search (nuts.rs:695-761, which in the reference never returns from such a start) ends with epsilon = 0, every
+ *   transition stops at its first leaf (1 leapfrog), every collected row is the start, bit for bit, and the run ends.
+ *   The other chains of the handle are not affected. */
 typedef struct mmcmc_nuts mmcmc_nuts;
 int mmcmc_nuts_create(mmcmc_nuts **out, const mmcmc_target_desc *target, const double *init, size_t n_chains,
                       double target_accept_p, int mode, int device);

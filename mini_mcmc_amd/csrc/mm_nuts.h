@@ -159,7 +159,12 @@ MM_HD ST mm_find_reasonable_epsilon(const mm_tparams<TT> &P, const TT *position,
     for (int i = 0; i < D; ++i)
         grad_real = grad_real && mm_is_real(g[i]);
     ST k = 1;
-    while (!mm_is_real(ulogp_p) && !grad_real) {
+    /* Not in the reference: `k > 0`.  A start whose own log-density is not real (a NaN or infinite coordinate, or a finite
+     * one where the density overflows TT) makes leap(0) non-real too, so without the bound this loop never ends -- the
+     * reference hangs a thread there, a kernel would hang the device.  Once k has underflowed to zero the step cannot
+     * change any more; every input on which the loop ended before leaves it at the same k.  Such a chain gets epsilon = 0:
+     * its joint density is never real, every tree stops at its first leaf, and the chain stays where it started. */
+    while (!mm_is_real(ulogp_p) && !grad_real && k > ST(0)) {
         k = k * half;
         ulogp_p = leap(epsilon * k);
     }
@@ -167,8 +172,18 @@ MM_HD ST mm_find_reasonable_epsilon(const mm_tparams<TT> &P, const TT *position,
     ST lap = (ST)(double)(ulogp_p - ulogp - (Red::dot(p, p) - mom_sq) * TT(0.5));
     const ST a = (lap > mm_logT(half)) ? ST(1) : ST(-1);
     const ST ln2 = mm_logT(ST(2));
+    /* Ends on every input.  A NaN lap fails the comparison at once.  Doubling (a = 1) reaches epsilon = inf after at most
+     * ~1100 steps; there the half step fma(inf, g, p) makes every momentum +-inf or NaN, so p.p is inf or NaN and lap is -inf
+     * or NaN, whatever the density is (flat included).  Halving (a = -1) reaches epsilon = 0, where the leapfrog is the
+     * identity and lap is 0, or NaN if the start or its gradient is not real.  The one state this does not cover is
+     * epsilon = 0 with a = 1 (the first loop ran k down to zero and leap(0) was real): doubling leaves 0 at 0.  So the loop
+     * also stops when the step no longer changes; from there leap, lap and the condition would repeat for ever, hence no
+     * input on which the loop ended before takes the new exit. */
     while (a * lap > -a * ln2) {
-        epsilon = (a > ST(0)) ? epsilon * ST(2) : epsilon * half; /* epsilon * 2^a */
+        const ST e2 = (a > ST(0)) ? epsilon * ST(2) : epsilon * half; /* epsilon * 2^a */
+        if (e2 == epsilon)
+            break;
+        epsilon = e2;
         ulogp_p = leap(epsilon);
         lap = (ST)(double)(ulogp_p - ulogp - (Red::dot(p, p) - mom_sq) * TT(0.5));
     }

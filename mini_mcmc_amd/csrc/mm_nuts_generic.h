@@ -110,7 +110,9 @@ template <class TT, class ST, class S> MM_HD ST mm_gen_find_reasonable_epsilon(i
     for (int i = 0; i < s.dim; ++i)
         grad_real = grad_real && mm_is_real(s.ld(MM_NV_CG, i));
     ST k = 1;
-    while (!mm_is_real(ulogp_p) && !grad_real) {
+    /* `k > 0` and the unchanged-step exit below: not in the reference; why both loops end is argued at
+     * mm_find_reasonable_epsilon (mm_nuts.h), of which this is the run-time-dimension copy */
+    while (!mm_is_real(ulogp_p) && !grad_real && k > ST(0)) {
         k = k * half;
         ulogp_p = leap(epsilon * k);
     }
@@ -119,7 +121,10 @@ template <class TT, class ST, class S> MM_HD ST mm_gen_find_reasonable_epsilon(i
     const ST a = (lap > mm_logT(half)) ? ST(1) : ST(-1);
     const ST ln2 = mm_logT(ST(2));
     while (a * lap > -a * ln2) {
-        epsilon = (a > ST(0)) ? epsilon * ST(2) : epsilon * half;
+        const ST e2 = (a > ST(0)) ? epsilon * ST(2) : epsilon * half;
+        if (e2 == epsilon)
+            break;
+        epsilon = e2;
         ulogp_p = leap(epsilon);
         lap = (ST)(double)(ulogp_p - ulogp - (mm_gen_dot<TT>(s, MM_NV_CP, MM_NV_CP) - mom_sq) * TT(0.5));
     }

@@ -451,6 +451,7 @@ int eh_noise(int dtype, uint64_t seed, uint64_t chain_offset, uint32_t iteration
     default:
         break;
     }
+#undef NOISE_CASE
     if (dim < 1)
         return -2;
     for (size_t i = 0; i < n; ++i) {
@@ -463,6 +464,23 @@ int eh_noise(int dtype, uint64_t seed, uint64_t chain_offset, uint32_t iteration
             mm_gen_noise(seed, chain_offset + i, iteration, dim, 0.0, [&](int k, double v) { zz[k] = v; });
             ((double *)u)[i] = mm_aux_u53(seed, chain_offset + i, iteration, 0);
         }
+    }
+    return 0;
+}
+
+/* ... as the MH sampler draws it (mm_mh_step): f32 at dim 1 and 2 takes the paired stream (mm_rng.h: mm_mh_paired), everything
+ * else the stream above */
+int eh_noise_mh(int dtype, uint64_t seed, uint64_t chain_offset, uint32_t iteration, size_t n, int dim, void *z, void *u)
+{
+    if (dtype != 0 || dim > 2)
+        return eh_noise(dtype, seed, chain_offset, iteration, n, dim, z, u);
+    if (dim < 1)
+        return -2;
+    for (size_t c = 0; c < n; ++c) {
+        if (dim == 1)
+            mm_draw_noise<1, mm_icdf_global, true>(seed, chain_offset + c, iteration, (float *)z + c, (float *)u + c);
+        else
+            mm_draw_noise<2, mm_icdf_global, true>(seed, chain_offset + c, iteration, (float *)z + 2 * c, (float *)u + c);
     }
     return 0;
 }

@@ -723,11 +723,16 @@ def engine_host_run(sampler, kind, dim, params, init, scale, n_collect, n_discar
     return out, state, acc
 
 
-def engine_host_noise(seed, chain_offset, iteration, n, dim, dtype=np.float32):
+def engine_host_noise(seed, chain_offset, iteration, n, dim, dtype=np.float32, sampler=""):
+    """(z [n, dim], u [n]) of one iteration; sampler "mh": as the MH sampler draws it (f32 at dim <= 2: the paired stream)"""
     E = engine_host_lib()
     z = np.empty((n, dim), dtype=dtype)
     u = np.empty(n, dtype=dtype)
-    rc = E.eh_noise(0 if dtype == np.float32 else 1, seed, chain_offset, iteration, n, dim, z.ctypes.data, u.ctypes.data)
+    fn = E.eh_noise
+    if sampler == "mh":
+        fn = E.eh_noise_mh
+        fn.restype, fn.argtypes = E.eh_noise.restype, E.eh_noise.argtypes
+    rc = fn(0 if dtype == np.float32 else 1, seed, chain_offset, iteration, n, dim, z.ctypes.data, u.ctypes.data)
     if rc != 0:
         raise ValueError(f"eh_noise: {rc}")
     return z, u
