@@ -44,7 +44,8 @@ extern "C" {
  *   mmcmc_hmc_group_set_step_size, mmcmc_hmc_group_set_n_leapfrog, mmcmc_mh_group_set_proposal_std,
  *   mmcmc_nuts_group_adapt_state, mmcmc_nuts_group_set_adapt_state, mmcmc_nuts_group_set_target_accept_p;
  *   rank-normalised diagnostics: mmcmc_rank_normalize, mmcmc_quantiles, mmcmc_rank_diagnostics;
- *   mmcmc_group_bind_collectives; the diagonal metric: mmcmc_{hmc,nuts}_set_metric, mmcmc_{hmc,nuts}_metric.
+ *   mmcmc_group_bind_collectives; the diagonal metric: mmcmc_{hmc,nuts}_set_metric, mmcmc_{hmc,nuts}_metric; the dense
+ *   metric: mmcmc_{hmc,nuts}_set_metric_dense, mmcmc_{hmc,nuts}_metric_dense.
  * A binding checks mmcmc_version() >= the version it was generated from (rust/mini-mcmc-hip: assert_abi, in every constructor). */
 #define MMCMC_VERSION 102 /* 0.1.2 */
 
@@ -226,6 +227,31 @@ int mmcmc_hmc_run_scheduled(mmcmc_hmc *h, size_t n_collect, size_t n_discard, co
  *     not, < 0 on error. */
 int mmcmc_hmc_set_metric(mmcmc_hmc *h, const double *scale); /* [dim], or NULL = identity */
 int mmcmc_hmc_metric(mmcmc_hmc *h, double *scale_out);
+/* A dense mass matrix from a Cholesky factor.  Additive as the diagonal metric: MMCMC_VERSION stays 102.
+ *   chol is a lower-triangular factor L, row-major [dim, dim] host doubles, with positive diagonal: Sigma = L L^T stands for the
+ *     posterior covariance, M = Sigma^-1, written in whitened momentum exactly as the diagonal metric is -- noise, kinetic
+ *     energy 1/2 sum p_i^2 and accept rule untouched:
+ *       HMC:  drift x_i = fma(eps, (L p)_i, x_i); kick p_j = fma(k, (L^T g)_j, p_j), k = eps / 2 for the first and the last kick
+ *             and eps for the merged ones;
+ *       NUTS: the leapfrog (and so the step-size search) with the same two products and eps signed; the stop criterion with
+ *             diff = L^-1 (x_plus - x_minus).  L^-1 is formed once, here, in float64 by forward substitution and then converted
+ *             to the tensor type.
+ *     Every sum starts at its diagonal term and takes the others by ascending index, each with one fma (mm_samplers.h):
+ *     an identity factor gives the bits of a handle without a metric, a factor diag(s) with every s_i a power of two the bits
+ *     of the diagonal metric s.
+ *   One metric per handle: a dense one replaces a diagonal one and the other way round; NULL to either setter removes
+ *     whichever is set, and the handle has the variant it had before.  What a metric applies to is as above.
+ *   Every check happens before any change.  MMCMC_ERR_INVALID_ARG: a non-finite entry, a non-zero entry above the diagonal, a
+ *     diagonal entry <= 0, a factor or inverse that is not finite with positive diagonal once converted to the handle's
+ *     element type (HMC) / tensor type (NUTS).  MMCMC_ERR_UNSUPPORTED, nothing changed: a dimension above 32, no run-time
+ *     compiler, a unit that fails its check.  Device groups and MH have no metric.
+ *   Kernels: a dense-metric unit of its own, compiled on the first set_metric_dense of a (target kind, dimension) and
+ *     verified bit for bit before the handle relies on it; the variant is 7 while the metric is set.
+ *   mmcmc_*_metric_dense writes chol_out[dim * dim], the doubles last set, and returns 1; returns 0 and writes nothing if no
+ *     dense metric is set; < 0 on error.  While a dense metric is set mmcmc_*_metric returns 2 and writes the marginal standard
+ *     deviations, the row norms of L. */
+int mmcmc_hmc_set_metric_dense(mmcmc_hmc *h, const double *chol); /* row-major dim x dim; NULL removes the metric */
+int mmcmc_hmc_metric_dense(mmcmc_hmc *h, double *chol_out);
 
 /* ---- NUTS ------------------------------------------------------------------------------------------------
  * NUTS::new(target, initial_positions, target_accept_p)   nuts.rs:123-129 over NUTSChain::new nuts.rs:410-434.
@@ -246,6 +272,9 @@ int mmcmc_nuts_create(mmcmc_nuts **out, const mmcmc_target_desc *target, const d
  * after the metric is set runs under it. */
 int mmcmc_nuts_set_metric(mmcmc_nuts *h, const double *scale); /* [dim], or NULL = identity */
 int mmcmc_nuts_metric(mmcmc_nuts *h, double *scale_out);
+/* the dense metric: see mmcmc_hmc_set_metric_dense */
+int mmcmc_nuts_set_metric_dense(mmcmc_nuts *h, const double *chol); /* row-major dim x dim; NULL removes the metric */
+int mmcmc_nuts_metric_dense(mmcmc_nuts *h, double *chol_out);
 /* NUTS::set_seed   nuts.rs:347-353 (keys the counter-based stream; chains differ by their global index) */
 int mmcmc_nuts_seed(mmcmc_nuts *h, uint64_t seed);
 int mmcmc_nuts_set_chain_offset(mmcmc_nuts *h, uint64_t chain_offset);

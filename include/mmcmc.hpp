@@ -439,7 +439,27 @@ template <class T> class HMC {
         if (st < 0)
             check(st, "mmcmc_hmc_metric");
         if (is_set)
-            *is_set = st == 1;
+            *is_set = st == 1; /* 2: a dense metric is set (metric_dense()), and these are the row norms of its factor */
+        return out;
+    }
+    /* the dense metric (mmcmc_hmc_set_metric_dense): a lower-triangular factor L, row-major [dim, dim], Sigma = L L^T; it
+     * replaces a diagonal metric, and clear_metric() removes either */
+    HMC &set_metric_dense(const std::vector<double> &chol)
+    {
+        if (chol.size() != dim_ * dim_)
+            throw Error(MMCMC_ERR_SHAPE, "HMC::set_metric_dense");
+        check(mmcmc_hmc_set_metric_dense(h_, chol.data()), "mmcmc_hmc_set_metric_dense");
+        return *this;
+    }
+    /* the factor last set, empty when no dense metric is set */
+    std::vector<double> metric_dense()
+    {
+        std::vector<double> out(dim_ * dim_);
+        const int st = mmcmc_hmc_metric_dense(h_, out.data());
+        if (st < 0)
+            check(st, "mmcmc_hmc_metric_dense");
+        if (st == 0)
+            out.clear();
         return out;
     }
     double step_size()
@@ -727,7 +747,27 @@ template <class T> class NUTS {
         if (st < 0)
             check(st, "mmcmc_nuts_metric");
         if (is_set)
-            *is_set = st == 1;
+            *is_set = st == 1; /* 2: a dense metric is set (metric_dense()), and these are the row norms of its factor */
+        return out;
+    }
+    /* the dense metric (mmcmc_nuts_set_metric_dense): a lower-triangular factor L, row-major [dim, dim], Sigma = L L^T; it
+     * replaces a diagonal metric, and clear_metric() removes either */
+    NUTS &set_metric_dense(const std::vector<double> &chol)
+    {
+        if (chol.size() != dim_ * dim_)
+            throw Error(MMCMC_ERR_SHAPE, "NUTS::set_metric_dense");
+        check(mmcmc_nuts_set_metric_dense(h_, chol.data()), "mmcmc_nuts_set_metric_dense");
+        return *this;
+    }
+    /* the factor last set, empty when no dense metric is set */
+    std::vector<double> metric_dense()
+    {
+        std::vector<double> out(dim_ * dim_);
+        const int st = mmcmc_nuts_metric_dense(h_, out.data());
+        if (st < 0)
+            check(st, "mmcmc_nuts_metric_dense");
+        if (st == 0)
+            out.clear();
         return out;
     }
     StreamPosition stream_position()
@@ -908,7 +948,27 @@ class NUTS64 {
         if (st < 0)
             check(st, "mmcmc_nuts_metric");
         if (is_set)
-            *is_set = st == 1;
+            *is_set = st == 1; /* 2: a dense metric is set (metric_dense()), and these are the row norms of its factor */
+        return out;
+    }
+    /* the dense metric (mmcmc_nuts_set_metric_dense): a lower-triangular factor L, row-major [dim, dim], Sigma = L L^T; it
+     * replaces a diagonal metric, and clear_metric() removes either */
+    NUTS64 &set_metric_dense(const std::vector<double> &chol)
+    {
+        if (chol.size() != dim_ * dim_)
+            throw Error(MMCMC_ERR_SHAPE, "NUTS64::set_metric_dense");
+        check(mmcmc_nuts_set_metric_dense(h_, chol.data()), "mmcmc_nuts_set_metric_dense");
+        return *this;
+    }
+    /* the factor last set, empty when no dense metric is set */
+    std::vector<double> metric_dense()
+    {
+        std::vector<double> out(dim_ * dim_);
+        const int st = mmcmc_nuts_metric_dense(h_, out.data());
+        if (st < 0)
+            check(st, "mmcmc_nuts_metric_dense");
+        if (st == 0)
+            out.clear();
         return out;
     }
     StreamPosition stream_position()

@@ -260,6 +260,11 @@ SIGNATURES = {
     "mmcmc_hmc_metric": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "mmcmc_nuts_set_metric": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "mmcmc_nuts_metric": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    # the dense metric (include/mmcmc.h: "A dense mass matrix from a Cholesky factor")
+    "mmcmc_hmc_set_metric_dense": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_hmc_metric_dense": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_nuts_set_metric_dense": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "mmcmc_nuts_metric_dense": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     # rank-normalised diagnostics (csrc/mm_rank.hip)
     "mmcmc_rank_normalize": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _vp, C.c_int, _vp,
                                        C.c_int, _vp]),

@@ -12,6 +12,8 @@ the caller's business.  Created over the same array, the handle continues bit fo
 
 A diagonal metric (`HMC.metric`, `NUTS.metric`) is part of a checkpoint: "metric", the scales as set, present only while one
 is set.  A checkpoint without the key -- every checkpoint written before metrics existed -- restores as "no metric".
+A dense metric (`HMC.metric_chol`, `NUTS.metric_chol`) is stored as "metric_chol", the factor as set, present only while a
+dense metric is set (a handle has one metric: "metric" is then absent).
 
 Not in a checkpoint: accept counts (per run), NUTS's cumulative leapfrog counts and depth histogram, tracker state
 (`MultiChainTracker`), the kernel variant and iters_per_launch (none of them changes a result).
@@ -164,7 +166,37 @@ def get_metric(obj):
     st = _fn(obj, "metric")(obj._h, out.ctypes.data_as(C.POINTER(C.c_double)))
     if st < 0:
         L.check(st, f"mmcmc_{obj._cprefix}_metric")
+    return out if st == 1 else None  # 2: a dense metric is set (get_metric_chol), not a diagonal one
+
+
+def get_metric_chol(obj):
+    """The dense metric of an HMC / NUTS handle: its factor [dim, dim] float64 exactly as set, or None when none is set."""
+    d = int(obj.dim)
+    out = np.empty((d, d), dtype=np.float64)
+    st = _fn(obj, "metric_dense")(obj._h, out.ctypes.data_as(C.POINTER(C.c_double)))
+    if st < 0:
+        L.check(st, f"mmcmc_{obj._cprefix}_metric_dense")
     return out if st == 1 else None
+
+
+def check_metric_chol(chol, dim: int) -> np.ndarray:
+    """[dim, dim] float64, finite, lower triangular with positive diagonal (the library checks the handle's type too)"""
+    a = np.ascontiguousarray(chol, dtype=np.float64)
+    if a.shape != (dim, dim):
+        raise ValueError(f"metric_chol: shape {a.shape} != ({dim}, {dim})")
+    if not np.all(np.isfinite(a)) or np.any(np.triu(a, 1) != 0) or not np.all(np.diag(a) > 0):
+        raise ValueError("metric_chol: a finite lower-triangular factor with positive diagonal is required")
+    return a
+
+
+def set_metric_chol(obj, chol) -> None:
+    """chol [dim, dim] lower triangular, or None to remove whichever metric is set; from the next transition on"""
+    name = f"mmcmc_{obj._cprefix}_set_metric_dense"
+    if chol is None:
+        L.check(_fn(obj, "set_metric_dense")(obj._h, None), name)
+        return
+    a = check_metric_chol(chol, int(obj.dim))
+    L.check(_fn(obj, "set_metric_dense")(obj._h, a.ctypes.data_as(C.POINTER(C.c_double))), name)
 
 
 def check_metric(scale, dim: int) -> np.ndarray:
@@ -206,6 +238,9 @@ def take(obj) -> dict:
         m = get_metric(obj)
         if m is not None:
             ck["metric"] = m
+        m = get_metric_chol(obj)
+        if m is not None:
+            ck["metric_chol"] = m
     return ck
 
 
@@ -244,6 +279,11 @@ def apply(obj, ck: dict) -> None:
         if not _has_metric(obj):
             raise ValueError("checkpoint: it holds a metric, this handle cannot take one")
         metric = check_metric(ck["metric"], dim)  # a wrong length is refused before anything is set
+    metric_chol = None
+    if "metric_chol" in ck:
+        if not _has_metric(obj) or metric is not None:
+            raise ValueError("checkpoint: it holds a dense metric, this handle cannot take it (or a diagonal one is stored too)")
+        metric_chol = check_metric_chol(ck["metric_chol"], dim)
     pos = np.asarray(ck["positions"])
     shape = (obj.n_chains,) if s == "mh_discrete" else (obj.n_chains, dim)
     if pos.shape != shape or pos.dtype != np.dtype(dt):
@@ -264,7 +304,10 @@ def apply(obj, ck: dict) -> None:
     if s == "nuts":
         set_adapt_array(obj, adapt)
     if _has_metric(obj):
-        set_metric(obj, metric)  # None (a checkpoint without one): no metric
+        if metric_chol is not None:
+            set_metric_chol(obj, metric_chol)
+        else:
+            set_metric(obj, metric)  # None (a checkpoint without one): no metric
 
 
 def save(path, ckpt: dict) -> None:

@@ -7,9 +7,11 @@
  */
 #include "../../include/mmcmc.h"
 #include "mm_host.h"
+#include "mm_dense_host.h"
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -184,6 +186,10 @@ struct Sampler {
     void *d_metric = nullptr;
     const mm_user_target *metric_unit = nullptr;
     int variant_before_metric = MM_VAR_PAIRED;
+    /* a dense metric instead (mmcmc_hmc_set_metric_dense; caps.dense next to caps.metric): the factor as given, row-major
+     * [dim, dim] (empty: none) -- d_metric then holds L packed by rows --, and the unit whose kernel reads it */
+    std::vector<double> metric_chol;
+    const mm_user_target *dense_unit = nullptr;
 
     size_t esize() const { return dtype == MMCMC_F32 ? 4 : 8; }
 };
@@ -564,6 +570,18 @@ int launch_range(Sampler *s, const mm_kernel_entry<T> *k, const mm_tparams<T> &P
                               mm_tile_lds_bytes_rt(sizeof(T), s->dim), stream);
         break;
     }
+    case MM_LAUNCH_DENSE_METRIC: {
+        /* the same skeleton with the dense metric, from the handle's dense-metric unit */
+        mm_run_dense_args<T> m;
+        m.a = a;
+        m.chol = (const T *)s->d_metric;
+        /* the body's dynamic LDS to a multiple of 16, then the staged factor (mm_kernels.h: mm_run_dense_lds) */
+        if (s->block != 64) /* mm_tile_lds_bytes_rt is the size for one wave per workgroup, which is what a unit is launched with */
+            return MMCMC_ERR_STATE;
+        e = mm_rtc_launch_run(s->dense_unit, 1, std::is_same<T, float>::value ? 0 : 1, &m, sizeof(m), grid, s->block,
+                              (mm_tile_lds_bytes_rt(sizeof(T), s->dim) + 15) / 16 * 16 + mm_tri_len((size_t)s->dim) * sizeof(T), stream);
+        break;
+    }
     case MM_LAUNCH_SEGMENTED: /* sampler_run runs such a schedule as unscheduled launches: sched_run is never set for it */
         return MMCMC_ERR_STATE;
     }
@@ -820,9 +838,11 @@ int sampler_timing(Sampler *s, mmcmc_timing *t)
  * parameter block (so a kind that carries data is checked on its data): up to 96 chains, 5 + 5 transitions with L = 3 from a
  * fixed start, (a) with a general metric twice -- the same bits --, (b) with a metric of all ones against the handle's
  * ordinary one-chain-per-lane kernel, which a ones-metric must reproduce bit for bit (mmcmc.h).  The handle's fields are
- * borrowed for the launches and put back.  Only real verdicts are cached. */
+ * borrowed for the launches and put back.  Only real verdicts are cached.
+ * dense: the dense-metric unit, checked the same way -- a general factor (large off-diagonal entries) twice, an identity
+ * factor against the ordinary kernel. */
 template <class T>
-bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tparams<T> &P, const mm_kernel_entry<T> *k)
+bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tparams<T> &P, const mm_kernel_entry<T> *k, bool dense = false)
 {
     static std::mutex mu;
     static std::map<std::pair<const void *, int>, bool> verdict;
@@ -834,12 +854,21 @@ bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tpara
             return it->second;
     }
     const size_t n = std::min<size_t>(96, s->n_chains), dim = (size_t)s->dim, nc = 5, nd = 5;
-    std::vector<T> x0(n * dim), ones(dim, T(1)), general(dim);
+    const size_t n_met = dense ? mm_tri_len(dim) : dim;
+    std::vector<T> x0(n * dim), ones(n_met, dense ? T(0) : T(1)), general(n_met);
     for (size_t c = 0; c < n; ++c)
         for (size_t i = 0; i < dim; ++i)
             x0[c * dim + i] = (T)(0.05 * (double)((int)((c * 7 + i * 13) % 17) - 8));
-    for (size_t i = 0; i < dim; ++i)
-        general[i] = (T)(0.75 + 0.125 * (double)(i % 5));
+    for (size_t i = 0; i < dim; ++i) {
+        if (!dense) {
+            general[i] = (T)(0.75 + 0.125 * (double)(i % 5));
+            continue;
+        }
+        ones[mm_tri_len(i) + i] = T(1);
+        general[mm_tri_len(i) + i] = (T)(0.75 + 0.125 * (double)(i % 5));
+        for (size_t j = 0; j < i; ++j)
+            general[mm_tri_len(i) + j] = (T)(0.5 * (double)((int)((i * 7 + j * 3) % 5) - 2) / std::sqrt((double)dim));
+    }
     /* the handle's fields the launches read, borrowed and put back */
     struct Borrow {
         Sampler *s;
@@ -848,17 +877,17 @@ bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tpara
         double scale;
         int n_leapfrog, variant;
         uint64_t seed, chain_offset, iter;
-        bool want_accept, metric;
-        const mm_user_target *unit;
+        bool want_accept, metric, dense;
+        const mm_user_target *unit, *dense_unit;
         const void *sched_run;
         ~Borrow()
         {
             s->d_state = d_state, s->d_metric = d_metric, s->n_chains = n_chains, s->scale = scale, s->n_leapfrog = n_leapfrog;
             s->variant = variant, s->seed = seed, s->chain_offset = chain_offset, s->iter = iter, s->want_accept = want_accept;
-            s->caps.metric = metric, s->metric_unit = unit, s->sched_run = sched_run;
+            s->caps.metric = metric, s->caps.dense = dense, s->metric_unit = unit, s->dense_unit = dense_unit, s->sched_run = sched_run;
         }
     } borrow{s, s->d_state, s->d_metric, s->n_chains, s->scale, s->n_leapfrog, s->variant, s->seed, s->chain_offset, s->iter,
-             s->want_accept, s->caps.metric, s->metric_unit, s->sched_run};
+             s->want_accept, s->caps.metric, s->caps.dense, s->metric_unit, s->dense_unit, s->sched_run};
     struct Dev {
         T *x = nullptr, *out = nullptr, *met = nullptr;
         ~Dev()
@@ -869,7 +898,7 @@ bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tpara
         }
     } d;
     if (hipMalloc((void **)&d.x, n * dim * sizeof(T)) != hipSuccess || hipMalloc((void **)&d.out, n * nc * dim * sizeof(T)) != hipSuccess ||
-        hipMalloc((void **)&d.met, dim * sizeof(T)) != hipSuccess)
+        hipMalloc((void **)&d.met, n_met * sizeof(T)) != hipSuccess)
         return false;
     s->d_state = d.x;
     s->d_metric = d.met;
@@ -880,7 +909,7 @@ bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tpara
     s->n_leapfrog = 3;
     s->want_accept = false;
     s->sched_run = nullptr;
-    s->metric_unit = unit;
+    (dense ? s->dense_unit : s->metric_unit) = unit;
     /* the one-chain-per-lane kernel the handle has without a metric: its unit, its fixed-dimension kernel, or run-time D */
     const int plain = s->caps.unit != MM_UNIT_NONE ? MM_VAR_UNIT : s->caps.fixed ? (s->dim > 16 ? MM_VAR_PLAIN : MM_VAR_PAIRED) : MM_VAR_GENERIC;
     /* metric == nullptr: the ordinary kernel */
@@ -888,8 +917,9 @@ bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tpara
         got.assign(n * nc * dim, T(0));
         s->iter = 0;
         s->caps.metric = metric != nullptr;
+        s->caps.dense = dense && metric != nullptr;
         s->variant = metric ? MM_VAR_UNIT : plain;
-        return (!metric || hipMemcpy(d.met, metric->data(), dim * sizeof(T), hipMemcpyHostToDevice) == hipSuccess) &&
+        return (!metric || hipMemcpy(d.met, metric->data(), n_met * sizeof(T), hipMemcpyHostToDevice) == hipSuccess) &&
                hipMemcpy(d.x, x0.data(), n * dim * sizeof(T), hipMemcpyHostToDevice) == hipSuccess &&
                launch_range<T>(s, k, P, d.out, nc, (uint32_t)nd, (uint32_t)nc, 0, s->stream) == MMCMC_OK &&
                hipStreamSynchronize(s->stream) == hipSuccess &&
@@ -910,9 +940,10 @@ int sampler_set_metric(Sampler *s, const double *scale)
 {
     if (!scale) { /* the identity: back to the variant the handle had */
         if (s->caps.metric) {
-            s->caps.metric = false;
+            s->caps.metric = s->caps.dense = false;
             s->variant = s->variant_before_metric;
             s->metric.clear();
+            s->metric_chol.clear();
         }
         return MMCMC_OK;
     }
@@ -936,8 +967,8 @@ int sampler_set_metric(Sampler *s, const double *scale)
     MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
     if (!(s->dtype == MMCMC_F32 ? metric_unit_verified<float>(s, unit, s->Pf, s->kf) : metric_unit_verified<double>(s, unit, s->Pd, s->kd)))
         return MMCMC_ERR_UNSUPPORTED;
-    if (!s->d_metric)
-        MM_HIP(hipMalloc(&s->d_metric, dim * s->esize()));
+    if (!s->d_metric) /* room for a dense metric's packed factor too */
+        MM_HIP(hipMalloc(&s->d_metric, mm_tri_len(dim) * s->esize()));
     if (s->dtype == MMCMC_F32) {
         std::vector<float> h(scale, scale + dim);
         MM_HIP(hipMemcpy(s->d_metric, h.data(), dim * sizeof(float), hipMemcpyHostToDevice));
@@ -946,12 +977,59 @@ int sampler_set_metric(Sampler *s, const double *scale)
     }
     s->metric_unit = unit;
     s->metric.assign(scale, scale + dim);
+    s->metric_chol.clear(); /* one metric per handle: a diagonal one replaces a dense one */
+    s->caps.dense = false;
     if (!s->caps.metric) {
         s->variant_before_metric = s->variant;
         s->caps.metric = true;
     }
     s->variant = MM_VAR_UNIT;
     return MMCMC_OK;
+}
+
+/* mmcmc_hmc_set_metric_dense: every check before any change */
+template <class T> int sampler_set_metric_dense_t(Sampler *s, const double *chol, const mm_tparams<T> &P, const mm_kernel_entry<T> *k)
+{
+    const size_t dim = (size_t)s->dim;
+    std::vector<T> l, li; /* li is NUTS's; forming it here keeps the checks the same for both samplers */
+    if (!mm_dense_prepare<T>(chol, dim, l, li))
+        return MMCMC_ERR_INVALID_ARG;
+    if (mm_metric_status(s->caps) != MMCMC_OK || s->block != 64) /* the unit's launch sizes its LDS for one wave per workgroup */
+        return MMCMC_ERR_UNSUPPORTED;
+    DevGuard g(s->device);
+    const mm_user_target *unit = s->dense_unit ? s->dense_unit : mm_rtc_dense_metric_unit(s->kind, s->dim);
+    if (!unit)
+        return MMCMC_ERR_UNSUPPORTED; /* no run-time compiler, a kind without a gradient functor, or the unit does not build */
+    MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
+    if (!metric_unit_verified<T>(s, unit, P, k, true))
+        return MMCMC_ERR_UNSUPPORTED;
+    if (!s->d_metric)
+        MM_HIP(hipMalloc(&s->d_metric, mm_tri_len(dim) * sizeof(T)));
+    MM_HIP(hipMemcpy(s->d_metric, l.data(), l.size() * sizeof(T), hipMemcpyHostToDevice));
+    s->dense_unit = unit;
+    s->metric_chol.assign(chol, chol + dim * dim);
+    s->metric.assign(dim, 0.0); /* what mmcmc_hmc_metric reports: the marginal standard deviations, the row norms of L */
+    for (size_t i = 0; i < dim; ++i) {
+        double q = 0.0;
+        for (size_t j = 0; j <= i; ++j)
+            q += chol[i * dim + j] * chol[i * dim + j];
+        s->metric[i] = std::sqrt(q);
+    }
+    if (!s->caps.metric) {
+        s->variant_before_metric = s->variant;
+        s->caps.metric = true;
+    }
+    s->caps.dense = true;
+    s->variant = MM_VAR_UNIT;
+    return MMCMC_OK;
+}
+int sampler_set_metric_dense(Sampler *s, const double *chol)
+{
+    if (!chol)
+        return sampler_set_metric(s, nullptr);
+    if (s->dim < 1) /* nothing to read */
+        return MMCMC_ERR_INVALID_ARG;
+    return s->dtype == MMCMC_F32 ? sampler_set_metric_dense_t<float>(s, chol, s->Pf, s->kf) : sampler_set_metric_dense_t<double>(s, chol, s->Pd, s->kd);
 }
 
 template <class T>
@@ -1396,7 +1474,18 @@ int mmcmc_hmc_metric(mmcmc_hmc *h, double *scale_out)
     const Sampler *s = h->s;
     for (int i = 0; i < s->dim; ++i)
         scale_out[i] = s->caps.metric ? s->metric[(size_t)i] : 1.0;
-    return s->caps.metric ? 1 : 0;
+    return s->caps.dense ? 2 : s->caps.metric ? 1 : 0;
+}
+int mmcmc_hmc_set_metric_dense(mmcmc_hmc *h, const double *chol) { return h ? sampler_set_metric_dense(h->s, chol) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_hmc_metric_dense(mmcmc_hmc *h, double *chol_out)
+{
+    if (!h || !chol_out)
+        return MMCMC_ERR_INVALID_ARG;
+    const Sampler *s = h->s;
+    if (!s->caps.dense)
+        return 0;
+    std::copy(s->metric_chol.begin(), s->metric_chol.end(), chol_out);
+    return 1;
 }
 int mmcmc_hmc_set_state(mmcmc_hmc *h, const void *positions, int is_device, void *stream)
 {

@@ -249,7 +249,7 @@ __device__ __forceinline__ void mm_flush_tile_raw(T *out, unsigned long long n_t
  * LCT > 0: compile-time leapfrog count (the loop is unrolled into that block).  Results are bit-identical for
  * every (PIPE, LCT): all variants evaluate the same functions (mm_rng.h, mm_samplers.h). */
 /* SCHED: HMC with PIPE = 2 only -- transition t takes (eps, L) from sched[t - sched_iter0] (mm_sched_at), run-time L */
-/* Met: HMC's metric (mm_samplers.h); mm_no_metric for every kernel of the library, a mm_diag_metric in mm_run_metric_body */
+/* Met: HMC's metric (mm_samplers.h); mm_no_metric for every kernel of the library, a mm_diag_metric in mm_run_metric_body, a mm_dense_metric in mm_run_dense_body */
 template <class T, class Tgt, int SAMPLER, int PIPE = 0, int LCT = 0, bool SCHED = false, class Met = mm_no_metric>
 __device__ __forceinline__ void mm_run_kernel_body(const mm_run_args<T> &a, const mm_sched_step<T> *sched = nullptr,
                                                    unsigned int sched_iter0 = 0, const Met &met = Met())
@@ -464,6 +464,33 @@ template <class T, class Tgt, int PIPE> __device__ __forceinline__ void mm_run_m
 {
     mm_diag_metric<T, Tgt::dim> met;
     mm_metric_load<Tgt::dim>(m.metric, met.s); /* r is NUTS's: never read here */
+    mm_run_kernel_body<T, Tgt, MM_SAMPLER_HMC, PIPE, 0, false>(m.a, nullptr, 0u, met);
+}
+
+/* HMC with a dense metric (mm_samplers.h: mm_dense_metric), in a run-time compiled unit of its own (mm_rtc.hip:
+ * mm_rtc_dense_metric_unit): mm_run_args followed by chol = L packed by rows, D (D + 1) / 2 elements of the element type,
+ * written by the host when the metric is set; the kernel stages it in LDS once per block and reads the entries from there.
+ * The copy lies in the dynamic LDS, behind what mm_run_kernel_body uses itself (launch_range asks for the body's bytes
+ * rounded up to 16 plus n elements: offset() below, with the host's run-time-dimension mirror mm_tile_lds_bytes_rt in its place): a static __shared__ array would move the dynamic part, and the f32 noise table must stay at LDS address 0
+ * (mm_icdf_lds_check traps otherwise). */
+template <class T, int D> struct mm_run_dense_lds {
+    static constexpr size_t n = (size_t)D * (D + 1) / 2;
+    __device__ static size_t offset(unsigned int block) /* the body's own bytes (mm_launch_run's formula), to a multiple of 16 */
+    {
+        return (mm_tile<T, D>::lds_bytes_table + (size_t)(block / 64) * mm_tile<T, D>::lds_bytes_per_wave + 15) / 16 * 16;
+    }
+};
+template <class T> struct mm_run_dense_args {
+    mm_run_args<T> a;
+    const T *chol;
+};
+template <class T, class Tgt, int PIPE> __device__ __forceinline__ void mm_run_dense_body(const mm_run_dense_args<T> &m)
+{
+    using Lds = mm_run_dense_lds<T, Tgt::dim>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char mm_lds_raw[];
+    T *fac = reinterpret_cast<T *>(mm_lds_raw + Lds::offset(blockDim.x));
+    mm_dense_stage(m.chol, fac, (int)Lds::n);
+    const mm_dense_metric<T, Tgt::dim> met(fac, nullptr); /* L^-1 is NUTS's: never read here */
     mm_run_kernel_body<T, Tgt, MM_SAMPLER_HMC, PIPE, 0, false>(m.a, nullptr, 0u, met);
 }
 

@@ -108,16 +108,25 @@ MM_HD TT mm_nuts_leapfrog(const mm_tparams<TT> &P, TT *x, TT *p, TT *g, TT eps, 
 {
     constexpr int D = Tgt::dim;
     const TT h = eps * TT(0.5);
-    MM_UNROLL
-    for (int i = 0; i < D; ++i) {
-        p[i] = mm_fma(mm_half_step_at(met, eps, h, i), g[i], p[i]);
-        x[i] = mm_fma(mm_step_at(met, eps, i), p[i], x[i]);
+    if constexpr (mm_metric_is_dense<Met>::value) {
+        /* a dense metric: p_j += h (L^T g)_j for every j, then x_i += eps (L p)_i, logp_grad, the second half kick */
+        mm_dense_kick(met, h, g, p);
+        mm_dense_drift(met, eps, p, x);
+        TT lp = Tgt::logp_grad(P, x, g);
+        mm_dense_kick(met, h, g, p);
+        return lp;
+    } else {
+        MM_UNROLL
+        for (int i = 0; i < D; ++i) {
+            p[i] = mm_fma(mm_half_step_at(met, eps, h, i), g[i], p[i]);
+            x[i] = mm_fma(mm_step_at(met, eps, i), p[i], x[i]);
+        }
+        TT lp = Tgt::logp_grad(P, x, g);
+        MM_UNROLL
+        for (int i = 0; i < D; ++i)
+            p[i] = mm_fma(mm_half_step_at(met, eps, h, i), g[i], p[i]);
+        return lp;
     }
-    TT lp = Tgt::logp_grad(P, x, g);
-    MM_UNROLL
-    for (int i = 0; i < D; ++i)
-        p[i] = mm_fma(mm_half_step_at(met, eps, h, i), g[i], p[i]);
-    return lp;
 }
 
 /* nuts.rs:963-977 */
@@ -128,9 +137,20 @@ template <class TT, int D, class Red, class Met = mm_no_metric>
 MM_HD bool mm_stop_criterion(const TT *x_minus, const TT *x_plus, const TT *p_minus, const TT *p_plus, const Met &met = Met())
 {
     TT diff[D];
-    MM_UNROLL
-    for (int i = 0; i < D; ++i)
-        diff[i] = mm_whiten_at(met, x_plus[i] - x_minus[i], i);
+    if constexpr (mm_metric_is_dense<Met>::value) {
+        /* diff = L^-1 (x_plus - x_minus), row by row in mm_tri_row_dot's order */
+        TT d[D];
+        MM_UNROLL
+        for (int i = 0; i < D; ++i)
+            d[i] = x_plus[i] - x_minus[i];
+        MM_UNROLL
+        for (int i = 0; i < D; ++i)
+            diff[i] = mm_tri_row_dot<D>(met.li, d, i);
+    } else {
+        MM_UNROLL
+        for (int i = 0; i < D; ++i)
+            diff[i] = mm_whiten_at(met, x_plus[i] - x_minus[i], i);
+    }
     return Red::dot(diff, p_minus) >= TT(0) && Red::dot(diff, p_plus) >= TT(0);
 }
 

@@ -4,10 +4,12 @@
  */
 #include "../../include/mmcmc.h"
 #include "mm_host.h"
+#include "mm_dense_host.h"
 #include "mm_hostcopy.h"
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -42,9 +44,14 @@ struct NutsBase {
     virtual int depth_histogram(uint32_t *out) = 0;
     virtual int set_variant(int v) = 0;
     virtual int set_metric(const double *scale) = 0;
+    virtual int set_metric_dense(const double *chol) = 0;
     /* the diagonal metric (mmcmc_nuts_set_metric): the scales as given while one is set, and the variant to return to */
     std::vector<double> metric;
     bool has_metric = false;
+    /* a dense metric instead (mmcmc_nuts_set_metric_dense): has_metric and has_dense, the factor as given, row-major [dim, dim];
+     * `metric` then holds the row norms of L, which mmcmc_nuts_metric reports */
+    bool has_dense = false;
+    std::vector<double> metric_chol;
     int variant_before_metric = 0;
     int variant = 0; /* 0: one chain per lane, lanes in step; 4: one chain per lane, asynchronous lanes (default for
                       * dim <= 8); 1: lane-group / MFMA (mm_nuts_lg.h); 2: + tree-depth compaction, one
@@ -84,7 +91,9 @@ template <class TT, class ST> struct Nuts : NutsBase {
     size_t user_stack_bytes = 0, user_lds = 0;
     /* with a metric: the unit whose kernels read it (mm_rtc_metric_unit), metric[2 dim] = s, then r = TT(1) / s, in the tensor type,
      * and the stack area of its kernels (a handle on a compiled instance keeps its stack in LDS and has none of its own) */
-    const mm_user_target *metric_unit = nullptr;
+    /* with a dense metric: its own unit (mm_rtc_dense_metric_unit); d_metric = L, then L^-1, each packed by rows (the buffer has
+     * room for either form: 2 mm_tri_len(dim) elements) */
+    const mm_user_target *metric_unit = nullptr, *dense_unit = nullptr;
     TT *d_metric = nullptr;
     unsigned char *d_metric_scratch = nullptr;
     TT *d_gstore = nullptr;
@@ -164,20 +173,36 @@ template <class TT, class ST> struct Nuts : NutsBase {
 
     /* the metric unit's kernels: init_chain, and a run by the pair kernel (which = 2: what handles launch) or with the lanes in
      * step (which = 0: the second opinion of metric_unit_verified); `scratch` = the stack area, one unit_sizes() block per wave */
-    hipError_t metric_init(const mm_user_target *unit, const mm_nuts_init_args<TT, ST> &ia, const TT *met, hipStream_t st)
+    /* dense: `unit` is a dense-metric unit and `met` = L, L^-1 packed by rows */
+    hipError_t metric_init(const mm_user_target *unit, const mm_nuts_init_args<TT, ST> &ia, const TT *met, hipStream_t st, bool dense = false)
     {
+        if (dense) {
+            mm_nuts_init_dense_args<TT, ST> m;
+            m.a = ia;
+            m.chol = met;
+            m.chol_inv = met + mm_tri_len((size_t)dim);
+            return mm_rtc_launch_nuts(unit, type_mode_of, 1, &m, sizeof(m), (unsigned int)((ia.n_chains + 63) / 64), 0, st);
+        }
         mm_nuts_init_metric_args<TT, ST> m;
         m.a = ia;
         m.metric = met;
         return mm_rtc_launch_nuts(unit, type_mode_of, 1, &m, sizeof(m), (unsigned int)((ia.n_chains + 63) / 64), 0, st);
     }
-    hipError_t metric_run(const mm_user_target *unit, const mm_nuts_args<TT, ST> &a, int which, const TT *met, hipStream_t st)
+    hipError_t metric_run(const mm_user_target *unit, const mm_nuts_args<TT, ST> &a, int which, const TT *met, hipStream_t st, bool dense = false)
     {
+        size_t stack = 0, tile = 0;
+        unit_sizes((size_t)dim, &stack, &tile);
+        if (dense) {
+            mm_nuts_dense_args<TT, ST> m;
+            m.a = a;
+            m.chol = met;
+            m.chol_inv = met + mm_tri_len((size_t)dim);
+            return mm_rtc_launch_nuts(unit, type_mode_of, which, &m, sizeof(m), (unsigned int)((a.n_chains + 63) / 64),
+                                      which == 2 ? (size_t)MM_NUTS_RING * 64 * sizeof(double) : tile, st);
+        }
         mm_nuts_metric_args<TT, ST> m;
         m.a = a;
         m.metric = met;
-        size_t stack = 0, tile = 0;
-        unit_sizes((size_t)dim, &stack, &tile);
         return mm_rtc_launch_nuts(unit, type_mode_of, which, &m, sizeof(m), (unsigned int)((a.n_chains + 63) / 64),
                                   which == 2 ? (size_t)MM_NUTS_RING * 64 * sizeof(double) : tile, st);
     }
@@ -186,8 +211,9 @@ template <class TT, class ST> struct Nuts : NutsBase {
      * rtc_unit_verified, on this handle's own parameter block (a kind that carries data is checked on its data): 96 chains,
      * 5 + 5 transitions from a fixed start under a general metric, (a) twice by the pair kernel -- the same bits --, (b) by
      * the unit's lanes-in-step kernel, which must agree bit for bit, under rtc_unit_verified's condition on the compiler
-     * that built the unit.  Only real verdicts are cached. */
-    bool metric_unit_verified(const mm_user_target *unit)
+     * that built the unit.  Only real verdicts are cached.
+     * dense: a dense-metric unit, checked the same way under a general factor with large off-diagonal entries. */
+    bool metric_unit_verified(const mm_user_target *unit, bool dense = false)
     {
         static std::mutex mu;
         static std::map<const void *, bool> verdict;
@@ -207,6 +233,19 @@ template <class TT, class ST> struct Nuts : NutsBase {
         for (size_t i = 0; i < D; ++i) {
             met[i] = (TT)(0.75 + 0.125 * (double)(i % 5));
             met[D + i] = TT(1) / met[i];
+        }
+        if (dense) {
+            std::vector<double> chol(D * D, 0.0);
+            for (size_t i = 0; i < D; ++i) {
+                chol[i * D + i] = 0.75 + 0.125 * (double)(i % 5);
+                for (size_t j = 0; j < i; ++j)
+                    chol[i * D + j] = 0.5 * (double)((int)((i * 7 + j * 3) % 5) - 2) / std::sqrt((double)D);
+            }
+            std::vector<TT> l, li;
+            if (!mm_dense_prepare<TT>(chol.data(), D, l, li))
+                return false;
+            met = l;
+            met.insert(met.end(), li.begin(), li.end());
         }
         std::vector<mm_nuts_adapt<ST>> ad0(n);
         for (auto &a : ad0) {
@@ -229,9 +268,9 @@ template <class TT, class ST> struct Nuts : NutsBase {
             }
         } d;
         if (hipMalloc((void **)&d.x, n * D * sizeof(TT)) != hipSuccess || hipMalloc((void **)&d.out, n * nc * D * sizeof(TT)) != hipSuccess ||
-            hipMalloc((void **)&d.met, 2 * D * sizeof(TT)) != hipSuccess || hipMalloc((void **)&d.ad, n * sizeof(mm_nuts_adapt<ST>)) != hipSuccess ||
+            hipMalloc((void **)&d.met, met.size() * sizeof(TT)) != hipSuccess || hipMalloc((void **)&d.ad, n * sizeof(mm_nuts_adapt<ST>)) != hipSuccess ||
             hipMalloc((void **)&d.scratch, waves * stack) != hipSuccess ||
-            hipMemcpy(d.met, met.data(), 2 * D * sizeof(TT), hipMemcpyHostToDevice) != hipSuccess)
+            hipMemcpy(d.met, met.data(), met.size() * sizeof(TT), hipMemcpyHostToDevice) != hipSuccess)
             return false;
         auto one = [&](int which, std::vector<TT> &got) -> bool {
             got.assign(n * nc * D, TT(0));
@@ -268,7 +307,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
             a.stack_in_lds = 0;
             a.async_batch = 0;
             a.scratch = d.scratch;
-            return metric_init(unit, ia, d.met, stream) == hipSuccess && metric_run(unit, a, which, d.met, stream) == hipSuccess &&
+            return metric_init(unit, ia, d.met, stream, dense) == hipSuccess && metric_run(unit, a, which, d.met, stream, dense) == hipSuccess &&
                    hipStreamSynchronize(stream) == hipSuccess &&
                    hipMemcpy(got.data(), d.out, got.size() * sizeof(TT), hipMemcpyDeviceToHost) == hipSuccess;
         };
@@ -294,9 +333,10 @@ template <class TT, class ST> struct Nuts : NutsBase {
     {
         if (!scale) {
             if (has_metric) {
-                has_metric = false;
+                has_metric = has_dense = false;
                 variant = variant_before_metric;
                 metric.clear();
+                metric_chol.clear();
             }
             return MMCMC_OK;
         }
@@ -317,8 +357,8 @@ template <class TT, class ST> struct Nuts : NutsBase {
         MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
         if (!metric_unit_verified(unit))
             return MMCMC_ERR_UNSUPPORTED;
-        if (!d_metric)
-            MM_HIP(hipMalloc((void **)&d_metric, 2 * D * sizeof(TT)));
+        if (!d_metric) /* room for a dense metric's two packed factors too */
+            MM_HIP(hipMalloc((void **)&d_metric, 2 * mm_tri_len(D) * sizeof(TT)));
         if (!d_metric_scratch) {
             size_t stack = 0, tile = 0;
             unit_sizes(D, &stack, &tile);
@@ -327,10 +367,59 @@ template <class TT, class ST> struct Nuts : NutsBase {
         MM_HIP(hipMemcpy(d_metric, h.data(), 2 * D * sizeof(TT), hipMemcpyHostToDevice));
         metric_unit = unit;
         metric.assign(scale, scale + D);
+        metric_chol.clear(); /* one metric per handle: a diagonal one replaces a dense one */
+        has_dense = false;
         if (!has_metric) {
             variant_before_metric = variant;
             has_metric = true;
         }
+        variant = 7;
+        return MMCMC_OK;
+    }
+
+    /* the same for a dense metric: chol = L row-major [dim, dim]; NULL removes whichever metric is set */
+    int set_metric_dense(const double *chol) override
+    {
+        if (!chol)
+            return set_metric(nullptr);
+        if (dim < 1)
+            return MMCMC_ERR_INVALID_ARG;
+        const size_t D = (size_t)dim;
+        std::vector<TT> l, li;
+        if (!mm_dense_prepare<TT>(chol, D, l, li))
+            return MMCMC_ERR_INVALID_ARG;
+        if (dim > 32)
+            return MMCMC_ERR_UNSUPPORTED;
+        DevGuard g(device);
+        const mm_user_target *unit = dense_unit ? dense_unit : mm_rtc_dense_metric_unit(kind, dim);
+        if (!unit)
+            return MMCMC_ERR_UNSUPPORTED; /* no run-time compiler (or the unit does not build): nothing changed */
+        MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
+        if (!metric_unit_verified(unit, true))
+            return MMCMC_ERR_UNSUPPORTED;
+        if (!d_metric)
+            MM_HIP(hipMalloc((void **)&d_metric, 2 * mm_tri_len(D) * sizeof(TT)));
+        if (!d_metric_scratch) {
+            size_t stack = 0, tile = 0;
+            unit_sizes(D, &stack, &tile);
+            MM_HIP(hipMalloc((void **)&d_metric_scratch, (n_chains + 63) / 64 * stack));
+        }
+        MM_HIP(hipMemcpy(d_metric, l.data(), l.size() * sizeof(TT), hipMemcpyHostToDevice));
+        MM_HIP(hipMemcpy(d_metric + l.size(), li.data(), li.size() * sizeof(TT), hipMemcpyHostToDevice));
+        dense_unit = unit;
+        metric_chol.assign(chol, chol + D * D);
+        metric.assign(D, 0.0); /* what mmcmc_nuts_metric reports: the marginal standard deviations, the row norms of L */
+        for (size_t i = 0; i < D; ++i) {
+            double q = 0.0;
+            for (size_t j = 0; j <= i; ++j)
+                q += chol[i * D + j] * chol[i * D + j];
+            metric[i] = std::sqrt(q);
+        }
+        if (!has_metric) {
+            variant_before_metric = variant;
+            has_metric = true;
+        }
+        has_dense = true;
         variant = 7;
         return MMCMC_OK;
     }
@@ -781,7 +870,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
             ia.seed = seed;
             ia.chain_offset = chain_offset;
             ia.eps_tol = sizeof(ST) == 4 ? (ST)1.1920929e-7 : (ST)2.220446049250313e-16;
-            e = has_metric ? metric_init(metric_unit, ia, d_metric, st) : mm_rtc_launch_nuts(user, type_mode, 1, &ia, sizeof(ia), grid64, 0, st);
+            e = has_metric ? metric_init(has_dense ? dense_unit : metric_unit, ia, d_metric, st, has_dense) : mm_rtc_launch_nuts(user, type_mode, 1, &ia, sizeof(ia), grid64, 0, st);
         } else {
             e = use_lg ? init_lg(st) : use_generic ? launch_generic(ga, 1, st) : k->init(P, d_state, d_adapt, n_chains, seed, chain_offset, st);
         }
@@ -837,7 +926,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
             /* the metric unit's pair kernel, its stack in the handle's metric scratch area */
             a.scratch = d_metric_scratch;
             a.stack_in_lds = 0;
-            e = metric_run(metric_unit, a, 2, d_metric, st);
+            e = metric_run(has_dense ? dense_unit : metric_unit, a, 2, d_metric, st, has_dense);
         } else if (rtc_target) {
             /* a run-time compiled target: asynchronous lanes with the leaves in pairs (mm_nuts_pair_body; dynamic LDS = the
              * ring of uniforms, stack in the scratch area).  The unit's lanes-in-step kernel (mm_nuts_run_body) is NOT
@@ -1181,7 +1270,17 @@ int mmcmc_nuts_metric(mmcmc_nuts *h, double *scale_out)
         return MMCMC_ERR_INVALID_ARG;
     for (int i = 0; i < h->p->dim; ++i)
         scale_out[i] = h->p->has_metric ? h->p->metric[(size_t)i] : 1.0;
-    return h->p->has_metric ? 1 : 0;
+    return h->p->has_dense ? 2 : h->p->has_metric ? 1 : 0;
+}
+int mmcmc_nuts_set_metric_dense(mmcmc_nuts *h, const double *chol) { return h ? h->p->set_metric_dense(chol) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_nuts_metric_dense(mmcmc_nuts *h, double *chol_out)
+{
+    if (!h || !chol_out)
+        return MMCMC_ERR_INVALID_ARG;
+    if (!h->p->has_dense)
+        return 0;
+    std::copy(h->p->metric_chol.begin(), h->p->metric_chol.end(), chol_out);
+    return 1;
 }
 int mmcmc_nuts_set_state(mmcmc_nuts *h, const void *x, int is_device, void *stream)
 {

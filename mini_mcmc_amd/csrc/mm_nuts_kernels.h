@@ -586,6 +586,41 @@ template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts
     mm_nuts_pair_body<TT, ST, Tgt, false>(m.a, mm_nuts_metric_of<TT, Tgt::dim>(m.metric));
 }
 
+/* The same with a dense metric (mm_samplers.h: mm_dense_metric), in the dense-metric unit (mm_rtc_dense_metric_unit): the
+ * existing argument blocks followed by chol = L and chol_inv = L^-1, each packed by rows, D (D + 1) / 2 elements of the tensor
+ * type, written by the host when the metric is set and staged in LDS once per block (mm_dense_stage): 2 D (D + 1) / 2 elements,
+ * 8448 bytes at D = 32 in f64.  The metric object is the two LDS pointers. */
+template <class TT, int D> __device__ __forceinline__ mm_dense_metric<TT, D> mm_nuts_dense_of(const TT *chol, const TT *chol_inv)
+{
+    constexpr int N = D * (D + 1) / 2;
+    __shared__ TT fac[2 * N];
+    mm_dense_stage(chol, fac, N);
+    mm_dense_stage(chol_inv, fac + N, N);
+    return mm_dense_metric<TT, D>(fac, fac + N);
+}
+template <class TT, class ST> struct mm_nuts_init_dense_args {
+    mm_nuts_init_args<TT, ST> a;
+    const TT *chol, *chol_inv;
+};
+template <class TT, class ST> struct mm_nuts_dense_args {
+    mm_nuts_args<TT, ST> a;
+    const TT *chol, *chol_inv;
+};
+template <class TT, class ST, class Tgt>
+__device__ __forceinline__ void mm_nuts_init_dense_body(const mm_nuts_init_dense_args<TT, ST> &m)
+{
+    mm_nuts_init_body<TT, ST, Tgt>(m.a.P, m.a.state, m.a.adapt, m.a.n_chains, m.a.seed, m.a.chain_offset, m.a.eps_tol,
+                                   mm_nuts_dense_of<TT, Tgt::dim>(m.chol, m.chol_inv));
+}
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_run_dense_body(const mm_nuts_dense_args<TT, ST> &m)
+{
+    mm_nuts_run_body<TT, ST, Tgt, false>(m.a, mm_nuts_dense_of<TT, Tgt::dim>(m.chol, m.chol_inv));
+}
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_pair_dense_body(const mm_nuts_dense_args<TT, ST> &m)
+{
+    mm_nuts_pair_body<TT, ST, Tgt, false>(m.a, mm_nuts_dense_of<TT, Tgt::dim>(m.chol, m.chol_inv));
+}
+
 #if !defined(__HIPCC_RTC__) /* host side: not part of the run-time compiled kernels of user targets (mm_rtc.hip) */
 template <class TT, class ST, class Tgt>
 hipError_t mm_launch_nuts_run_pair(const mm_nuts_args<TT, ST> &a, hipStream_t stream)

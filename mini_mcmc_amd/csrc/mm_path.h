@@ -48,6 +48,8 @@ struct mm_path_caps {
     bool few_chains = false;  /* dim >= 128 && n_chains < 1024: where the wide kernel is the default */
     bool metric = false;      /* HMC: a diagonal metric is set (mmcmc_hmc_set_metric): the handle runs its metric unit, variant 7,
                                  whatever it ran before; cleared again with the metric */
+    bool dense = false;       /* ... and it is a dense one (mmcmc_hmc_set_metric_dense): only with `metric`; the same rule, the kernel
+                                 of the handle's dense-metric unit */
 };
 
 /* one enumerator per launcher launch_range can call */
@@ -64,7 +66,8 @@ enum mm_launch {
     MM_LAUNCH_WIDE,        /* mm_launch_hmc_wide_* */
     MM_LAUNCH_LG,          /* mm_launch_hmc_lg / mm_launch_hmc_lg32 */
     MM_LAUNCH_SEGMENTED,   /* a scheduled run without a scheduled kernel: one unscheduled launch per run of equal (eps, L) */
-    MM_LAUNCH_METRIC       /* the HMC kernel of the handle's metric unit (mm_rtc_metric_unit): mm_rtc_launch_run with mm_run_metric_args */
+    MM_LAUNCH_METRIC,      /* the HMC kernel of the handle's metric unit (mm_rtc_metric_unit): mm_rtc_launch_run with mm_run_metric_args */
+    MM_LAUNCH_DENSE_METRIC /* the one of its dense-metric unit (mm_rtc_dense_metric_unit): mm_rtc_launch_run with mm_run_dense_args */
 };
 
 /* no fixed-dimension kernel and not a caller's unit: the run-time-dimension kernel is what the handle falls back on */
@@ -94,6 +97,8 @@ static inline bool mm_path_caps_consistent(const mm_path_caps &c)
         return false;
     if (c.metric && (!hmc || c.dim > 32))
         return false; /* mm_metric_status refused it */
+    if (c.dense && !c.metric)
+        return false; /* a dense metric is a metric */
     return true;
 }
 
@@ -156,7 +161,7 @@ static inline mm_launch mm_launch_path(const mm_path_caps &c, int variant, int n
 {
     const bool hmc = c.sampler == MM_SAMPLER_HMC, l10 = hmc && n_leapfrog == 10;
     if (c.metric) /* one kernel, run-time L; a schedule goes through the segmented fallback */
-        return scheduled ? MM_LAUNCH_SEGMENTED : MM_LAUNCH_METRIC;
+        return scheduled ? MM_LAUNCH_SEGMENTED : c.dense ? MM_LAUNCH_DENSE_METRIC : MM_LAUNCH_METRIC;
     if (scheduled) {
         /* kernels that read the schedule on the device: the split kernel and PIPE = 2 of the fixed-dimension targets */
         if (hmc && c.fixed && variant == MM_VAR_SPLIT && c.split_sched)

@@ -271,6 +271,85 @@ template <int D, class T> MM_HD void mm_metric_load(const T *__restrict__ base, 
         out[i] = p[i];
 }
 
+/* A dense metric: a lower-triangular factor L with positive diagonal, Sigma = L L^T standing for the posterior covariance,
+ * M = Sigma^-1 written in whitened momentum as above: the drift moves x by eps * (L p), a kick moves p by k * (L^T g), and
+ * NUTS's stop criterion takes diff = L^-1 (x_plus - x_minus).  l and li are L and L^-1, each packed by rows -- element (i, j),
+ * j <= i, at i (i + 1) / 2 + j, D (D + 1) / 2 elements -- in the element / tensor type, written by the host when the metric
+ * is set.  The object is the two base pointers, not a copy (at D = 32 the factors are 1056 elements and mm_nuts_tree : Met is
+ * per lane).  On the device they point into LDS: a kernel stages the factors once per block (mm_dense_stage) and every lane
+ * of a wave reads the same address at a compile-time offset -- a broadcast read.  Reading them through the constant address
+ * space instead, as mm_metric_load does, was built first and is right up to dim 24, but at dim 32 the compiler hoists the
+ * 528 scalar loads of a product and spills them (1200 - 2500 SGPR spills per kernel against 60 - 200 of the diagonal unit),
+ * and the NUTS kernels of that build gave wrong samples on the device.
+ * Order of the sums, fixed: every sum starts at its diagonal term, then takes the others by ascending index with mm_fma --
+ *   (L p)_i    = L_ii p_i,  then j = 0 .. i-1:    fma(L_ij, p_j, .)        (and L^-1 d alike)
+ *   (L^T g)_j  = L_jj g_j,  then i = j+1 .. D-1:  fma(L_ij, g_i, .)
+ * so an identity factor gives the bits of no metric (1 * p_i, then + 0 * p_j) and a factor diag(s) with powers of two the
+ * bits of the diagonal metric s (the scalings are exact: fma(eps, s_i p_i, x_i) = fma(eps s_i, p_i, x_i)). */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MM_FACTOR_AS __attribute__((address_space(3)))
+#else
+#define MM_FACTOR_AS
+#endif
+template <class T, int D> struct mm_dense_metric {
+    static constexpr bool on = true;
+    const T MM_FACTOR_AS *l = nullptr;
+    const T MM_FACTOR_AS *li = nullptr;
+    mm_dense_metric() = default;
+    /* on the device l_ and li_ MUST point into LDS (what mm_dense_stage filled): the casts below keep the low 32 bits of the
+     * address, which is meaningless for a pointer to global memory; on the host they are ordinary pointers */
+    MM_HD mm_dense_metric(const T *l_, const T *li_) : l((const T MM_FACTOR_AS *)l_), li((const T MM_FACTOR_AS *)li_) {}
+};
+template <class Met> struct mm_metric_is_dense {
+    static constexpr bool value = false;
+};
+template <class T, int D> struct mm_metric_is_dense<mm_dense_metric<T, D>> {
+    static constexpr bool value = true;
+};
+/* row i of a packed lower-triangular factor times v: f_ii v_i first, then j = 0 .. i-1 */
+template <int D, class T> MM_HD T mm_tri_row_dot(const T MM_FACTOR_AS *f, const T *v, int i)
+{
+    const int r = i * (i + 1) / 2;
+    T s = f[r + i] * v[i];
+    MM_UNROLL
+    for (int j = 0; j < D; ++j)
+        if (j < i)
+            s = mm_fma(f[r + j], v[j], s);
+    return s;
+}
+/* column j of it times v, (f^T v)_j: f_jj v_j first, then i = j+1 .. D-1 */
+template <int D, class T> MM_HD T mm_tri_col_dot(const T MM_FACTOR_AS *f, const T *v, int j)
+{
+    T s = f[j * (j + 1) / 2 + j] * v[j];
+    MM_UNROLL
+    for (int i = 0; i < D; ++i)
+        if (i > j)
+            s = mm_fma(f[i * (i + 1) / 2 + j], v[i], s);
+    return s;
+}
+/* drift x_i = fma(eps, (L p)_i, x_i): p is only read.  kick p_j = fma(k, (L^T g)_j, p_j): g is only read. */
+template <class T, int D> MM_HD void mm_dense_drift(const mm_dense_metric<T, D> &m, T eps, const T *p, T *x)
+{
+    MM_UNROLL
+    for (int i = 0; i < D; ++i)
+        x[i] = mm_fma(eps, mm_tri_row_dot<D>(m.l, p, i), x[i]);
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+/* dst[0 .. n) = src[0 .. n) by the whole block, dst in LDS, then the barrier: every thread of the block calls it */
+template <class T> __device__ __forceinline__ void mm_dense_stage(const T *__restrict__ src, T *dst, int n)
+{
+    for (int i = threadIdx.x; i < n; i += blockDim.x)
+        dst[i] = src[i];
+    __syncthreads();
+}
+#endif
+template <class T, int D> MM_HD void mm_dense_kick(const mm_dense_metric<T, D> &m, T k, const T *g, T *p)
+{
+    MM_UNROLL
+    for (int j = 0; j < D; ++j)
+        p[j] = mm_fma(k, mm_tri_col_dot<D>(m.l, g, j), p[j]);
+}
+
 /* One HMC transition given its noise: p[D] ~ N(0,1) (momentum; clobbered) and ln_u.  x[D], lp = logp(x),
  * g = grad logp(x) are updated in place; returns 1 on accept. */
 struct mm_no_hook {
@@ -282,7 +361,8 @@ struct mm_no_hook {
  * iterations' Philox rounds through here was measured (tools/hmc_split.hip) and is slower, DESIGN.md 5.1. */
 /* Met: the metric (above).  mm_no_metric: the scalar eps for every coordinate, the expressions below as they always were.
  * mm_diag_metric: e_i = eps * s_i (one multiplication in T), h_i = e_i / 2 in their place; noise, kinetic energy and accept
- * rule are the same -- HMC with M = diag(1 / s_i^2) in whitened momentum. */
+ * rule are the same -- HMC with M = diag(1 / s_i^2) in whitened momentum.  mm_dense_metric: the drift and the kicks are the
+ * two triangular products (mm_dense_drift, mm_dense_kick) with the scalar eps, h and k. */
 template <class T, class Tgt, int LCT = 0, class Red = mm_red_seq<T, Tgt::dim>, class Hook = mm_no_hook, class Met = mm_no_metric>
 MM_HD int mm_hmc_step_noise(const mm_tparams<T> &P, T eps, int n_leapfrog, T *x, T *lp, T *g, T *p, T ln_u,
                             Hook &&hook = Hook(), unsigned int *n_accepted = nullptr, const Met &met = Met())
@@ -306,28 +386,44 @@ MM_HD int mm_hmc_step_noise(const mm_tparams<T> &P, T eps, int n_leapfrog, T *x,
      * step and the start kick of the next use the same gradient and are merged here into one kick by eps (SURVEY
      * App. B Q6: allowed on the GPU, the oracle keeps them apart; the results differ by rounding only) */
     auto leap = [&](bool last) {
-        MM_UNROLL
-        for (int i = 0; i < D; ++i)
-            xn[i] = mm_fma(mm_step_at(met, eps, i), p[i], xn[i]); /* drift */
+        if constexpr (mm_metric_is_dense<Met>::value) {
+            mm_dense_drift(met, eps, p, xn);
+        } else {
+            MM_UNROLL
+            for (int i = 0; i < D; ++i)
+                xn[i] = mm_fma(mm_step_at(met, eps, i), p[i], xn[i]); /* drift */
+        }
         lpn = Tgt::logp_grad(P, xn, gn);
         const T k = last ? h : eps;
-        MM_UNROLL
-        for (int i = 0; i < D; ++i)
-            p[i] = mm_fma(mm_kick_at(met, eps, k, last, i), gn[i], p[i]);
+        if constexpr (mm_metric_is_dense<Met>::value) {
+            mm_dense_kick(met, k, gn, p);
+        } else {
+            MM_UNROLL
+            for (int i = 0; i < D; ++i)
+                p[i] = mm_fma(mm_kick_at(met, eps, k, last, i), gn[i], p[i]);
+        }
     };
     if constexpr (LCT > 0) {
-        MM_UNROLL
-        for (int i = 0; i < D; ++i)
-            p[i] = mm_fma(mm_half_step_at(met, eps, h, i), gn[i], p[i]); /* first half kick, with the gradient of the current position */
+        if constexpr (mm_metric_is_dense<Met>::value) {
+            mm_dense_kick(met, h, gn, p);
+        } else {
+            MM_UNROLL
+            for (int i = 0; i < D; ++i)
+                p[i] = mm_fma(mm_half_step_at(met, eps, h, i), gn[i], p[i]); /* first half kick, with the gradient of the current position */
+        }
         MM_UNROLL
         for (int l = 0; l < LCT; ++l) {
             leap(l + 1 == LCT);
             hook(l);
         }
     } else if (n_leapfrog > 0) {
-        MM_UNROLL
-        for (int i = 0; i < D; ++i)
-            p[i] = mm_fma(mm_half_step_at(met, eps, h, i), gn[i], p[i]);
+        if constexpr (mm_metric_is_dense<Met>::value) {
+            mm_dense_kick(met, h, gn, p);
+        } else {
+            MM_UNROLL
+            for (int i = 0; i < D; ++i)
+                p[i] = mm_fma(mm_half_step_at(met, eps, h, i), gn[i], p[i]);
+        }
         for (int l = 0; l < n_leapfrog; ++l) {
             leap(l + 1 == n_leapfrog);
             hook(l);

@@ -102,6 +102,20 @@ class HMC(_Sampler):
         K.set_metric(self, scale)
 
     @property
+    def metric_chol(self):
+        """The dense metric: a lower-triangular factor L [dim, dim] float64 with positive diagonal -- Sigma = L L^T stands for
+        the posterior covariance, M = Sigma^-1 in whitened momentum: the drift moves x by step_size * (L p), a kick moves p
+        by k * (L^T g) --, or None when none is set; the getter returns exactly what was set.  A handle has one metric:
+        setting this replaces a diagonal `metric` and the other way round, and None to either removes whichever is set.
+        An identity factor gives the bits of no metric.  Up to dim 32; the first use compiles the target's dense-metric
+        unit (seconds); kernel_variant is 7 while a metric is set (warmup.warmup_hmc(..., dense=True))."""
+        return K.get_metric_chol(self)
+
+    @metric_chol.setter
+    def metric_chol(self, chol) -> None:
+        K.set_metric_chol(self, chol)
+
+    @property
     def positions(self) -> np.ndarray:
         """hmc.rs:49 `positions` [n_chains, D]."""
         return self.state()

@@ -153,6 +153,20 @@ class NUTS(K.Checkpointable):
     def metric(self, scale) -> None:
         K.set_metric(self, scale)
 
+    @property
+    def metric_chol(self):
+        """The dense metric: a lower-triangular factor L [dim, dim] float64 with positive diagonal (Sigma = L L^T stands for the
+        posterior covariance; the leapfrog drifts by epsilon * (L p) and kicks by (epsilon / 2) * (L^T g), the stop criterion
+        takes L^-1 (x+ - x-)), or None when none is set; the getter returns exactly what was set.  A handle has one
+        metric: setting this replaces a diagonal `metric` and the other way round, None to either removes whichever is
+        set.  Seed, iteration and adaptation records are untouched (warmup.warmup_nuts(..., dense=True) resets epsilon to
+        the sentinel).  Up to dim 32; the first use compiles the target's dense-metric unit (seconds)."""
+        return K.get_metric_chol(self)
+
+    @metric_chol.setter
+    def metric_chol(self, chol) -> None:
+        K.set_metric_chol(self, chol)
+
     def _params(self):
         p, d = C.c_double(), C.c_int()
         L.check(L.lib().mmcmc_nuts_params(self._h, C.byref(p), C.byref(d)), "mmcmc_nuts_params")

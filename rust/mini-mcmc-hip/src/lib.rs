@@ -263,6 +263,29 @@ impl<T: GpuFloat> GpuHmc<T> {
         let owned = positions.as_standard_layout();
         check(unsafe { sys::mmcmc_hmc_set_state(self.h, owned.as_ptr() as *const c_void, 0, null_mut()) })
     }
+    /// A dense metric from a lower-triangular Cholesky factor `[dim, dim]` (`mmcmc_hmc_set_metric_dense`), `None` removes
+    /// whichever metric is set
+    pub fn set_metric_dense(&mut self, chol: Option<&Array2<f64>>) -> Result<(), MmcmcError> {
+        match chol {
+            None => check(unsafe { sys::mmcmc_hmc_set_metric_dense(self.h, std::ptr::null()) }),
+            Some(c) => {
+                if c.dim() != (self.dim, self.dim) {
+                    return check(sys::MMCMC_ERR_SHAPE);
+                }
+                let owned = c.as_standard_layout();
+                check(unsafe { sys::mmcmc_hmc_set_metric_dense(self.h, owned.as_ptr()) })
+            }
+        }
+    }
+    /// the factor last set, `None` when no dense metric is set (`mmcmc_hmc_metric_dense`)
+    pub fn metric_dense(&self) -> Result<Option<Array2<f64>>, MmcmcError> {
+        let mut out = Array2::<f64>::zeros((self.dim, self.dim));
+        let st = unsafe { sys::mmcmc_hmc_metric_dense(self.h, out.as_mut_ptr()) };
+        if st < 0 {
+            check(st)?;
+        }
+        Ok(if st == 1 { Some(out) } else { None })
+    }
     /// Transition k uses `(step_sizes[k], n_leapfrogs[k])`; the first `len - n_collect` are discarded: bit for bit the loop
     /// `set_step_size; set_n_leapfrog; step()` in one call (`mmcmc_hmc_run_scheduled`), `[n_chains, n_collect, dim]`
     pub fn run_scheduled(&mut self, step_sizes: &[f64], n_leapfrogs: &[i32], n_collect: usize) -> Result<Array3<T>, MmcmcError> {
@@ -734,6 +757,29 @@ impl GpuNuts {
         }
         let owned = adapt.as_standard_layout();
         check(unsafe { sys::mmcmc_nuts_set_adapt_state(self.h, owned.as_ptr()) })
+    }
+    /// A dense metric from a lower-triangular Cholesky factor `[dim, dim]` (`mmcmc_nuts_set_metric_dense`), `None` removes
+    /// whichever metric is set
+    pub fn set_metric_dense(&mut self, chol: Option<&Array2<f64>>) -> Result<(), MmcmcError> {
+        match chol {
+            None => check(unsafe { sys::mmcmc_nuts_set_metric_dense(self.h, std::ptr::null()) }),
+            Some(c) => {
+                if c.dim() != (self.dim, self.dim) {
+                    return check(sys::MMCMC_ERR_SHAPE);
+                }
+                let owned = c.as_standard_layout();
+                check(unsafe { sys::mmcmc_nuts_set_metric_dense(self.h, owned.as_ptr()) })
+            }
+        }
+    }
+    /// the factor last set, `None` when no dense metric is set (`mmcmc_nuts_metric_dense`)
+    pub fn metric_dense(&self) -> Result<Option<Array2<f64>>, MmcmcError> {
+        let mut out = Array2::<f64>::zeros((self.dim, self.dim));
+        let st = unsafe { sys::mmcmc_nuts_metric_dense(self.h, out.as_mut_ptr()) };
+        if st < 0 {
+            check(st)?;
+        }
+        Ok(if st == 1 { Some(out) } else { None })
     }
     /// the iteration is `self.m` (the adaptation reads it against n_discard)
     pub fn stream_position(&self) -> Result<StreamPosition, MmcmcError> {
