@@ -7,7 +7,7 @@
  */
 #include "../../include/mmcmc.h"
 #include "mm_host.h"
-#include "mm_dense_host.h"
+#include "mm_metric_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -180,19 +180,23 @@ struct Sampler {
     /* set for the duration of a scheduled run whose variant has a scheduled kernel: launch_range launches it */
     const void *sched_run = nullptr;
     uint32_t sched_iter0 = 0;
-    /* HMC's diagonal metric (mmcmc_hmc_set_metric): the scales as given (empty: none), their device image in the handle's
-     * element type [dim], the unit whose kernel reads it, and the variant to return to when the metric is cleared */
-    std::vector<double> metric;
+    /* HMC's metric (mmcmc_hmc_set_metric, _set_metric_dense): the record of what is set (mm_metric_host.h; caps.metric and
+     * caps.dense follow its kind, sync_metric_caps), the device image in the handle's element type -- s [dim], or L packed by
+     * rows; room for either --, and the diagonal and the dense unit whose kernels read it */
+    mm_metric_record met;
     void *d_metric = nullptr;
-    const mm_user_target *metric_unit = nullptr;
-    int variant_before_metric = MM_VAR_PAIRED;
-    /* a dense metric instead (mmcmc_hmc_set_metric_dense; caps.dense next to caps.metric): the factor as given, row-major
-     * [dim, dim] (empty: none) -- d_metric then holds L packed by rows --, and the unit whose kernel reads it */
-    std::vector<double> metric_chol;
-    const mm_user_target *dense_unit = nullptr;
+    const mm_user_target *metric_unit = nullptr, *dense_unit = nullptr;
 
     size_t esize() const { return dtype == MMCMC_F32 ? 4 : 8; }
 };
+static_assert(MM_VAR_UNIT == mm_metric_variant, "a handle with a metric is on its metric unit");
+
+/* the one place where the path rule's two metric facts are assigned */
+void sync_metric_caps(Sampler *s)
+{
+    s->caps.metric = s->met.kind != MM_METRIC_NONE;
+    s->caps.dense = s->met.kind == MM_METRIC_DENSE;
+}
 
 int sampler_create(Sampler **out, int sampler, const mmcmc_target_desc *target, double scale, int n_leapfrog,
                    const void *init, size_t n_chains, int dtype, int device);
@@ -561,25 +565,27 @@ int launch_range(Sampler *s, const mm_kernel_entry<T> *k, const mm_tparams<T> &P
             e = mm_launch_hmc_lg32(s->dim, q, stream);
         break;
     }
-    case MM_LAUNCH_METRIC: {
-        /* the one-wave-per-SIMD skeleton around the target's functor with the metric, from the handle's metric unit */
-        mm_run_metric_args<T> m;
-        m.a = a;
-        m.metric = (const T *)s->d_metric;
-        e = mm_rtc_launch_run(s->metric_unit, 1, std::is_same<T, float>::value ? 0 : 1, &m, sizeof(m), grid, s->block,
-                              mm_tile_lds_bytes_rt(sizeof(T), s->dim), stream);
-        break;
-    }
+    case MM_LAUNCH_METRIC:
     case MM_LAUNCH_DENSE_METRIC: {
-        /* the same skeleton with the dense metric, from the handle's dense-metric unit */
-        mm_run_dense_args<T> m;
-        m.a = a;
-        m.chol = (const T *)s->d_metric;
-        /* the body's dynamic LDS to a multiple of 16, then the staged factor (mm_kernels.h: mm_run_dense_lds) */
-        if (s->block != 64) /* mm_tile_lds_bytes_rt is the size for one wave per workgroup, which is what a unit is launched with */
-            return MMCMC_ERR_STATE;
-        e = mm_rtc_launch_run(s->dense_unit, 1, std::is_same<T, float>::value ? 0 : 1, &m, sizeof(m), grid, s->block,
-                              (mm_tile_lds_bytes_rt(sizeof(T), s->dim) + 15) / 16 * 16 + mm_tri_len((size_t)s->dim) * sizeof(T), stream);
+        /* the one-wave-per-SIMD skeleton around the target's functor with the metric, from the handle's diagonal or dense unit:
+         * the kind decides which argument block is filled, and for a dense metric adds the staged factor to the LDS */
+        mm_run_metric_args<T> md;
+        mm_run_dense_args<T> mL;
+        void *m = &md;
+        size_t m_bytes = sizeof(md), lds = mm_tile_lds_bytes_rt(sizeof(T), s->dim);
+        if (!s->caps.dense) {
+            md.a = a;
+            md.metric = (const T *)s->d_metric;
+        } else {
+            if (s->block != 64) /* mm_tile_lds_bytes_rt is the size for one wave per workgroup, which is what a unit is launched with */
+                return MMCMC_ERR_STATE;
+            mL.a = a;
+            mL.chol = (const T *)s->d_metric;
+            m = &mL, m_bytes = sizeof(mL);
+            /* the body's dynamic LDS to a multiple of 16, then the staged factor (mm_kernels.h: mm_run_dense_lds) */
+            lds = (lds + 15) / 16 * 16 + mm_tri_len((size_t)s->dim) * sizeof(T);
+        }
+        e = mm_rtc_launch_run(s->caps.dense ? s->dense_unit : s->metric_unit, 1, std::is_same<T, float>::value ? 0 : 1, m, m_bytes, grid, s->block, lds, stream);
         break;
     }
     case MM_LAUNCH_SEGMENTED: /* sampler_run runs such a schedule as unscheduled launches: sched_run is never set for it */
@@ -842,7 +848,7 @@ int sampler_timing(Sampler *s, mmcmc_timing *t)
  * dense: the dense-metric unit, checked the same way -- a general factor (large off-diagonal entries) twice, an identity
  * factor against the ordinary kernel. */
 template <class T>
-bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tparams<T> &P, const mm_kernel_entry<T> *k, bool dense = false)
+bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tparams<T> &P, const mm_kernel_entry<T> *k, bool dense)
 {
     static std::mutex mu;
     static std::map<std::pair<const void *, int>, bool> verdict;
@@ -855,39 +861,34 @@ bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tpara
     }
     const size_t n = std::min<size_t>(96, s->n_chains), dim = (size_t)s->dim, nc = 5, nd = 5;
     const size_t n_met = dense ? mm_tri_len(dim) : dim;
-    std::vector<T> x0(n * dim), ones(n_met, dense ? T(0) : T(1)), general(n_met);
-    for (size_t c = 0; c < n; ++c)
-        for (size_t i = 0; i < dim; ++i)
-            x0[c * dim + i] = (T)(0.05 * (double)((int)((c * 7 + i * 13) % 17) - 8));
-    for (size_t i = 0; i < dim; ++i) {
-        if (!dense) {
-            general[i] = (T)(0.75 + 0.125 * (double)(i % 5));
-            continue;
-        }
+    /* the probe inputs of mm_metric_host.h as the images a setter would upload; `ones` = no metric in either form */
+    const std::vector<double> start = mm_probe_start(n, dim);
+    const std::vector<T> x0(start.begin(), start.end());
+    std::vector<T> ones(n_met, dense ? T(0) : T(1)), general, li;
+    for (size_t i = 0; dense && i < dim; ++i)
         ones[mm_tri_len(i) + i] = T(1);
-        general[mm_tri_len(i) + i] = (T)(0.75 + 0.125 * (double)(i % 5));
-        for (size_t j = 0; j < i; ++j)
-            general[mm_tri_len(i) + j] = (T)(0.5 * (double)((int)((i * 7 + j * 3) % 5) - 2) / std::sqrt((double)dim));
-    }
+    if (dense ? !mm_dense_prepare<T>(mm_probe_chol(dim).data(), dim, general, li) : !mm_diag_prepare<T>(mm_probe_scale(dim).data(), dim, false, general))
+        return false;
     /* the handle's fields the launches read, borrowed and put back */
     struct Borrow {
         Sampler *s;
         void *d_state, *d_metric;
         size_t n_chains;
         double scale;
-        int n_leapfrog, variant;
+        int n_leapfrog, variant, met_kind;
         uint64_t seed, chain_offset, iter;
-        bool want_accept, metric, dense;
+        bool want_accept;
         const mm_user_target *unit, *dense_unit;
         const void *sched_run;
         ~Borrow()
         {
             s->d_state = d_state, s->d_metric = d_metric, s->n_chains = n_chains, s->scale = scale, s->n_leapfrog = n_leapfrog;
             s->variant = variant, s->seed = seed, s->chain_offset = chain_offset, s->iter = iter, s->want_accept = want_accept;
-            s->caps.metric = metric, s->caps.dense = dense, s->metric_unit = unit, s->dense_unit = dense_unit, s->sched_run = sched_run;
+            s->met.kind = met_kind, s->metric_unit = unit, s->dense_unit = dense_unit, s->sched_run = sched_run;
+            sync_metric_caps(s);
         }
-    } borrow{s, s->d_state, s->d_metric, s->n_chains, s->scale, s->n_leapfrog, s->variant, s->seed, s->chain_offset, s->iter,
-             s->want_accept, s->caps.metric, s->caps.dense, s->metric_unit, s->dense_unit, s->sched_run};
+    } borrow{s, s->d_state, s->d_metric, s->n_chains, s->scale, s->n_leapfrog, s->variant, s->met.kind, s->seed, s->chain_offset, s->iter,
+             s->want_accept, s->metric_unit, s->dense_unit, s->sched_run};
     struct Dev {
         T *x = nullptr, *out = nullptr, *met = nullptr;
         ~Dev()
@@ -916,8 +917,8 @@ bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tpara
     auto one = [&](const std::vector<T> *metric, std::vector<T> &got) -> bool {
         got.assign(n * nc * dim, T(0));
         s->iter = 0;
-        s->caps.metric = metric != nullptr;
-        s->caps.dense = dense && metric != nullptr;
+        s->met.kind = !metric ? MM_METRIC_NONE : dense ? MM_METRIC_DENSE : MM_METRIC_DIAG;
+        sync_metric_caps(s);
         s->variant = metric ? MM_VAR_UNIT : plain;
         return (!metric || hipMemcpy(d.met, metric->data(), n_met * sizeof(T), hipMemcpyHostToDevice) == hipSuccess) &&
                hipMemcpy(d.x, x0.data(), n * dim * sizeof(T), hipMemcpyHostToDevice) == hipSuccess &&
@@ -935,101 +936,53 @@ bool metric_unit_verified(Sampler *s, const mm_user_target *unit, const mm_tpara
     return ok;
 }
 
-/* mmcmc_hmc_set_metric: every check before any change */
-int sampler_set_metric(Sampler *s, const double *scale)
+/* mmcmc_hmc_set_metric (dense = false: values = the scales [dim]) and mmcmc_hmc_set_metric_dense (values = L row-major
+ * [dim, dim]): every check before any change, nothing changed on any refusal */
+template <class T> int sampler_set_metric_t(Sampler *s, bool dense, const double *values)
 {
-    if (!scale) { /* the identity: back to the variant the handle had */
-        if (s->caps.metric) {
-            s->caps.metric = s->caps.dense = false;
-            s->variant = s->variant_before_metric;
-            s->metric.clear();
-            s->metric_chol.clear();
-        }
+    const size_t dim = (size_t)s->dim;
+    /* HMC's kernels never read r_i = 1 / s_i, so the diagonal image is s alone (mm_diag_prepare); li is NUTS's, and forming it
+     * here keeps the dense checks the same for both samplers */
+    std::vector<T> image, li;
+    if (dense ? !mm_dense_prepare<T>(values, dim, image, li) : !mm_diag_prepare<T>(values, dim, false, image))
+        return MMCMC_ERR_INVALID_ARG;
+    /* the dense unit's launch sizes its LDS for one wave per workgroup */
+    if (mm_metric_status(s->caps) != MMCMC_OK || (dense && s->block != 64))
+        return MMCMC_ERR_UNSUPPORTED;
+    DevGuard g(s->device);
+    const mm_user_target *&kept = dense ? s->dense_unit : s->metric_unit;
+    const mm_user_target *unit = kept ? kept : mm_rtc_metric_unit(s->kind, s->dim, dense);
+    if (!unit) /* no run-time compiler, a kind without a gradient functor (a model's handle carries the model's kind), or the unit does not build */
+        return MMCMC_ERR_UNSUPPORTED;
+    MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
+    bool verified;
+    if constexpr (std::is_same<T, float>::value)
+        verified = metric_unit_verified<float>(s, unit, s->Pf, s->kf, dense);
+    else
+        verified = metric_unit_verified<double>(s, unit, s->Pd, s->kd, dense);
+    if (!verified)
+        return MMCMC_ERR_UNSUPPORTED;
+    if (!s->d_metric) /* room for either kind: a dense metric's packed factor */
+        MM_HIP(hipMalloc(&s->d_metric, mm_tri_len(dim) * sizeof(T)));
+    MM_HIP(hipMemcpy(s->d_metric, image.data(), image.size() * sizeof(T), hipMemcpyHostToDevice));
+    kept = unit;
+    if (dense)
+        s->met.commit_dense(values, dim, s->variant);
+    else
+        s->met.commit_diag(values, dim, s->variant);
+    sync_metric_caps(s);
+    return MMCMC_OK;
+}
+int sampler_set_metric(Sampler *s, bool dense, const double *values)
+{
+    if (!values) { /* the identity, through either entry point: back to the variant the handle had */
+        s->met.clear(s->variant);
+        sync_metric_caps(s);
         return MMCMC_OK;
     }
-    const size_t dim = (size_t)s->dim;
-    for (size_t i = 0; i < dim; ++i) {
-        const double v = scale[i];
-        const double as_t = s->dtype == MMCMC_F32 ? (double)(float)v : v; /* finite and > 0 in the handle's element type too */
-        if (!std::isfinite(v) || !(v > 0.0) || !std::isfinite(as_t) || !(as_t > 0.0))
-            return MMCMC_ERR_INVALID_ARG;
-    }
-    if (mm_metric_status(s->caps) != MMCMC_OK)
-        return MMCMC_ERR_UNSUPPORTED;
-    DevGuard g(s->device);
-    const mm_user_target *unit = s->metric_unit;
-    if (!unit) {
-        /* a model's handle carries the model's kind, which has no gradient functor: mm_rtc_metric_unit answers NULL */
-        unit = mm_rtc_metric_unit(s->kind, s->dim);
-        if (!unit)
-            return MMCMC_ERR_UNSUPPORTED; /* no run-time compiler (or the unit does not build): nothing changed */
-    }
-    MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
-    if (!(s->dtype == MMCMC_F32 ? metric_unit_verified<float>(s, unit, s->Pf, s->kf) : metric_unit_verified<double>(s, unit, s->Pd, s->kd)))
-        return MMCMC_ERR_UNSUPPORTED;
-    if (!s->d_metric) /* room for a dense metric's packed factor too */
-        MM_HIP(hipMalloc(&s->d_metric, mm_tri_len(dim) * s->esize()));
-    if (s->dtype == MMCMC_F32) {
-        std::vector<float> h(scale, scale + dim);
-        MM_HIP(hipMemcpy(s->d_metric, h.data(), dim * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-        MM_HIP(hipMemcpy(s->d_metric, scale, dim * sizeof(double), hipMemcpyHostToDevice));
-    }
-    s->metric_unit = unit;
-    s->metric.assign(scale, scale + dim);
-    s->metric_chol.clear(); /* one metric per handle: a diagonal one replaces a dense one */
-    s->caps.dense = false;
-    if (!s->caps.metric) {
-        s->variant_before_metric = s->variant;
-        s->caps.metric = true;
-    }
-    s->variant = MM_VAR_UNIT;
-    return MMCMC_OK;
-}
-
-/* mmcmc_hmc_set_metric_dense: every check before any change */
-template <class T> int sampler_set_metric_dense_t(Sampler *s, const double *chol, const mm_tparams<T> &P, const mm_kernel_entry<T> *k)
-{
-    const size_t dim = (size_t)s->dim;
-    std::vector<T> l, li; /* li is NUTS's; forming it here keeps the checks the same for both samplers */
-    if (!mm_dense_prepare<T>(chol, dim, l, li))
+    if (dense && s->dim < 1) /* nothing to read */
         return MMCMC_ERR_INVALID_ARG;
-    if (mm_metric_status(s->caps) != MMCMC_OK || s->block != 64) /* the unit's launch sizes its LDS for one wave per workgroup */
-        return MMCMC_ERR_UNSUPPORTED;
-    DevGuard g(s->device);
-    const mm_user_target *unit = s->dense_unit ? s->dense_unit : mm_rtc_dense_metric_unit(s->kind, s->dim);
-    if (!unit)
-        return MMCMC_ERR_UNSUPPORTED; /* no run-time compiler, a kind without a gradient functor, or the unit does not build */
-    MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
-    if (!metric_unit_verified<T>(s, unit, P, k, true))
-        return MMCMC_ERR_UNSUPPORTED;
-    if (!s->d_metric)
-        MM_HIP(hipMalloc(&s->d_metric, mm_tri_len(dim) * sizeof(T)));
-    MM_HIP(hipMemcpy(s->d_metric, l.data(), l.size() * sizeof(T), hipMemcpyHostToDevice));
-    s->dense_unit = unit;
-    s->metric_chol.assign(chol, chol + dim * dim);
-    s->metric.assign(dim, 0.0); /* what mmcmc_hmc_metric reports: the marginal standard deviations, the row norms of L */
-    for (size_t i = 0; i < dim; ++i) {
-        double q = 0.0;
-        for (size_t j = 0; j <= i; ++j)
-            q += chol[i * dim + j] * chol[i * dim + j];
-        s->metric[i] = std::sqrt(q);
-    }
-    if (!s->caps.metric) {
-        s->variant_before_metric = s->variant;
-        s->caps.metric = true;
-    }
-    s->caps.dense = true;
-    s->variant = MM_VAR_UNIT;
-    return MMCMC_OK;
-}
-int sampler_set_metric_dense(Sampler *s, const double *chol)
-{
-    if (!chol)
-        return sampler_set_metric(s, nullptr);
-    if (s->dim < 1) /* nothing to read */
-        return MMCMC_ERR_INVALID_ARG;
-    return s->dtype == MMCMC_F32 ? sampler_set_metric_dense_t<float>(s, chol, s->Pf, s->kf) : sampler_set_metric_dense_t<double>(s, chol, s->Pd, s->kd);
+    return s->dtype == MMCMC_F32 ? sampler_set_metric_t<float>(s, dense, values) : sampler_set_metric_t<double>(s, dense, values);
 }
 
 template <class T>
@@ -1466,27 +1419,13 @@ int mmcmc_hmc_params(mmcmc_hmc *h, double *step_size, int *n_leapfrog)
         *n_leapfrog = h->s->n_leapfrog;
     return MMCMC_OK;
 }
-int mmcmc_hmc_set_metric(mmcmc_hmc *h, const double *scale) { return h ? sampler_set_metric(h->s, scale) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_hmc_set_metric(mmcmc_hmc *h, const double *scale) { return h ? sampler_set_metric(h->s, false, scale) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_hmc_metric(mmcmc_hmc *h, double *scale_out)
 {
-    if (!h || !scale_out)
-        return MMCMC_ERR_INVALID_ARG;
-    const Sampler *s = h->s;
-    for (int i = 0; i < s->dim; ++i)
-        scale_out[i] = s->caps.metric ? s->metric[(size_t)i] : 1.0;
-    return s->caps.dense ? 2 : s->caps.metric ? 1 : 0;
+    return h && scale_out ? h->s->met.report_scale(scale_out, (size_t)h->s->dim) : MMCMC_ERR_INVALID_ARG;
 }
-int mmcmc_hmc_set_metric_dense(mmcmc_hmc *h, const double *chol) { return h ? sampler_set_metric_dense(h->s, chol) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_hmc_metric_dense(mmcmc_hmc *h, double *chol_out)
-{
-    if (!h || !chol_out)
-        return MMCMC_ERR_INVALID_ARG;
-    const Sampler *s = h->s;
-    if (!s->caps.dense)
-        return 0;
-    std::copy(s->metric_chol.begin(), s->metric_chol.end(), chol_out);
-    return 1;
-}
+int mmcmc_hmc_set_metric_dense(mmcmc_hmc *h, const double *chol) { return h ? sampler_set_metric(h->s, true, chol) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_hmc_metric_dense(mmcmc_hmc *h, double *chol_out) { return h && chol_out ? h->s->met.report_chol(chol_out) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_hmc_set_state(mmcmc_hmc *h, const void *positions, int is_device, void *stream)
 {
     return h ? sampler_set_state(h->s, positions, is_device, stream) : MMCMC_ERR_INVALID_ARG;

@@ -4,7 +4,7 @@
  */
 #include "../../include/mmcmc.h"
 #include "mm_host.h"
-#include "mm_dense_host.h"
+#include "mm_metric_host.h"
 #include "mm_hostcopy.h"
 
 #include <hip/hip_runtime.h>
@@ -43,16 +43,8 @@ struct NutsBase {
     virtual int leapfrog_counts(uint64_t *out) = 0;
     virtual int depth_histogram(uint32_t *out) = 0;
     virtual int set_variant(int v) = 0;
-    virtual int set_metric(const double *scale) = 0;
-    virtual int set_metric_dense(const double *chol) = 0;
-    /* the diagonal metric (mmcmc_nuts_set_metric): the scales as given while one is set, and the variant to return to */
-    std::vector<double> metric;
-    bool has_metric = false;
-    /* a dense metric instead (mmcmc_nuts_set_metric_dense): has_metric and has_dense, the factor as given, row-major [dim, dim];
-     * `metric` then holds the row norms of L, which mmcmc_nuts_metric reports */
-    bool has_dense = false;
-    std::vector<double> metric_chol;
-    int variant_before_metric = 0;
+    virtual int set_metric(bool dense, const double *values) = 0;
+    mm_metric_record met; /* the metric that is set (mmcmc_nuts_set_metric, _set_metric_dense; mm_metric_host.h) */
     int variant = 0; /* 0: one chain per lane, lanes in step; 4: one chain per lane, asynchronous lanes (default for
                       * dim <= 8); 1: lane-group / MFMA (mm_nuts_lg.h); 2: + tree-depth compaction, one
                         launch per level; 3: + compaction by a persistent scheduler */
@@ -89,10 +81,10 @@ template <class TT, class ST> struct Nuts : NutsBase {
     bool generic_ok = false;
     const mm_user_target *user = nullptr; /* run-time compiled target (mm_rtc.hip, variant 7) */
     size_t user_stack_bytes = 0, user_lds = 0;
-    /* with a metric: the unit whose kernels read it (mm_rtc_metric_unit), metric[2 dim] = s, then r = TT(1) / s, in the tensor type,
-     * and the stack area of its kernels (a handle on a compiled instance keeps its stack in LDS and has none of its own) */
-    /* with a dense metric: its own unit (mm_rtc_dense_metric_unit); d_metric = L, then L^-1, each packed by rows (the buffer has
-     * room for either form: 2 mm_tri_len(dim) elements) */
+    /* with a metric: the diagonal or the dense unit whose kernels read it (mm_rtc_metric_unit), d_metric = s, then r = TT(1) / s,
+     * or L, then L^-1, each packed by rows, in the tensor type (metric_image; the buffer has room for either form: 2
+     * mm_tri_len(dim) elements), and the stack area of the units' kernels (a handle on a compiled instance keeps its stack in LDS
+     * and has none of its own) */
     const mm_user_target *metric_unit = nullptr, *dense_unit = nullptr;
     TT *d_metric = nullptr;
     unsigned char *d_metric_scratch = nullptr;
@@ -171,40 +163,38 @@ template <class TT, class ST> struct Nuts : NutsBase {
 
     static constexpr int type_mode_of = std::is_same<TT, double>::value ? 2 : (std::is_same<ST, double>::value ? 0 : 1);
 
-    /* the metric unit's kernels: init_chain, and a run by the pair kernel (which = 2: what handles launch) or with the lanes in
-     * step (which = 0: the second opinion of metric_unit_verified); `scratch` = the stack area, one unit_sizes() block per wave */
-    /* dense: `unit` is a dense-metric unit and `met` = L, L^-1 packed by rows */
-    hipError_t metric_init(const mm_user_target *unit, const mm_nuts_init_args<TT, ST> &ia, const TT *met, hipStream_t st, bool dense = false)
+    /* the kernels of the handle's metric unit (the dense one while a dense metric is set, `dense`): init_chain, and a run by
+     * the pair kernel (which = 2: what handles launch) or with the lanes in step (which = 0: the second opinion of
+     * metric_unit_verified); `scratch` = the stack area, one unit_sizes() block per wave.  met = s, r (diagonal) or L, L^-1
+     * packed by rows (dense): the kind decides which argument block is filled, the launch is the same */
+    template <class Diag, class Dense, class A>
+    hipError_t metric_launch(const mm_user_target *unit, bool dense, const A &a, int which, const TT *met, size_t lds, hipStream_t st)
     {
-        if (dense) {
-            mm_nuts_init_dense_args<TT, ST> m;
-            m.a = ia;
-            m.chol = met;
-            m.chol_inv = met + mm_tri_len((size_t)dim);
-            return mm_rtc_launch_nuts(unit, type_mode_of, 1, &m, sizeof(m), (unsigned int)((ia.n_chains + 63) / 64), 0, st);
+        Diag md;
+        Dense mL;
+        void *m = &md;
+        size_t m_bytes = sizeof(md);
+        if (!dense) {
+            md.a = a;
+            md.metric = met;
+        } else {
+            mL.a = a;
+            mL.chol = met;
+            mL.chol_inv = met + mm_tri_len((size_t)dim);
+            m = &mL, m_bytes = sizeof(mL);
         }
-        mm_nuts_init_metric_args<TT, ST> m;
-        m.a = ia;
-        m.metric = met;
-        return mm_rtc_launch_nuts(unit, type_mode_of, 1, &m, sizeof(m), (unsigned int)((ia.n_chains + 63) / 64), 0, st);
+        return mm_rtc_launch_nuts(unit, type_mode_of, which, m, m_bytes, (unsigned int)((a.n_chains + 63) / 64), lds, st);
     }
-    hipError_t metric_run(const mm_user_target *unit, const mm_nuts_args<TT, ST> &a, int which, const TT *met, hipStream_t st, bool dense = false)
+    hipError_t metric_init(const mm_user_target *unit, const mm_nuts_init_args<TT, ST> &ia, const TT *met, hipStream_t st, bool dense)
+    {
+        return metric_launch<mm_nuts_init_metric_args<TT, ST>, mm_nuts_init_dense_args<TT, ST>>(unit, dense, ia, 1, met, 0, st);
+    }
+    hipError_t metric_run(const mm_user_target *unit, const mm_nuts_args<TT, ST> &a, int which, const TT *met, hipStream_t st, bool dense)
     {
         size_t stack = 0, tile = 0;
         unit_sizes((size_t)dim, &stack, &tile);
-        if (dense) {
-            mm_nuts_dense_args<TT, ST> m;
-            m.a = a;
-            m.chol = met;
-            m.chol_inv = met + mm_tri_len((size_t)dim);
-            return mm_rtc_launch_nuts(unit, type_mode_of, which, &m, sizeof(m), (unsigned int)((a.n_chains + 63) / 64),
-                                      which == 2 ? (size_t)MM_NUTS_RING * 64 * sizeof(double) : tile, st);
-        }
-        mm_nuts_metric_args<TT, ST> m;
-        m.a = a;
-        m.metric = met;
-        return mm_rtc_launch_nuts(unit, type_mode_of, which, &m, sizeof(m), (unsigned int)((a.n_chains + 63) / 64),
-                                  which == 2 ? (size_t)MM_NUTS_RING * 64 * sizeof(double) : tile, st);
+        return metric_launch<mm_nuts_metric_args<TT, ST>, mm_nuts_dense_args<TT, ST>>(unit, dense, a, which, met,
+                                                                                     which == 2 ? (size_t)MM_NUTS_RING * 64 * sizeof(double) : tile, st);
     }
 
     /* The metric unit is checked once per (unit, type mode) and process before a handle relies on it, like the units of
@@ -213,7 +203,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
      * the unit's lanes-in-step kernel, which must agree bit for bit, under rtc_unit_verified's condition on the compiler
      * that built the unit.  Only real verdicts are cached.
      * dense: a dense-metric unit, checked the same way under a general factor with large off-diagonal entries. */
-    bool metric_unit_verified(const mm_user_target *unit, bool dense = false)
+    bool metric_unit_verified(const mm_user_target *unit, bool dense)
     {
         static std::mutex mu;
         static std::map<const void *, bool> verdict;
@@ -226,27 +216,12 @@ template <class TT, class ST> struct Nuts : NutsBase {
         const size_t n = 96, D = (size_t)dim, nc = 5, nd = 5, waves = (n + 63) / 64;
         size_t stack = 0, tile = 0;
         unit_sizes(D, &stack, &tile);
-        std::vector<TT> x0(n * D), met(2 * D);
-        for (size_t c = 0; c < n; ++c)
-            for (size_t i = 0; i < D; ++i)
-                x0[c * D + i] = (TT)(0.05 * (double)((int)((c * 7 + i * 13) % 17) - 8));
-        for (size_t i = 0; i < D; ++i) {
-            met[i] = (TT)(0.75 + 0.125 * (double)(i % 5));
-            met[D + i] = TT(1) / met[i];
-        }
-        if (dense) {
-            std::vector<double> chol(D * D, 0.0);
-            for (size_t i = 0; i < D; ++i) {
-                chol[i * D + i] = 0.75 + 0.125 * (double)(i % 5);
-                for (size_t j = 0; j < i; ++j)
-                    chol[i * D + j] = 0.5 * (double)((int)((i * 7 + j * 3) % 5) - 2) / std::sqrt((double)D);
-            }
-            std::vector<TT> l, li;
-            if (!mm_dense_prepare<TT>(chol.data(), D, l, li))
-                return false;
-            met = l;
-            met.insert(met.end(), li.begin(), li.end());
-        }
+        /* the probe inputs of mm_metric_host.h, as the image a setter would upload */
+        const std::vector<double> start = mm_probe_start(n, D);
+        const std::vector<TT> x0(start.begin(), start.end());
+        std::vector<TT> met;
+        if (!metric_image(dense, (dense ? mm_probe_chol(D) : mm_probe_scale(D)).data(), met))
+            return false;
         std::vector<mm_nuts_adapt<ST>> ad0(n);
         for (auto &a : ad0) {
             a.epsilon = (ST)-1;
@@ -328,99 +303,57 @@ template <class TT, class ST> struct Nuts : NutsBase {
         return ok;
     }
 
-    /* every value is checked before anything changes; NULL removes the metric and gives the handle its variant back */
-    int set_metric(const double *scale) override
+    /* the checks of a metric's values and its device image in the tensor type: s, then r (with the inverse: the stop criterion
+     * multiplies by r_i), or L, then L^-1, each packed by rows */
+    bool metric_image(bool dense, const double *values, std::vector<TT> &image) const
     {
-        if (!scale) {
-            if (has_metric) {
-                has_metric = has_dense = false;
-                variant = variant_before_metric;
-                metric.clear();
-                metric_chol.clear();
-            }
-            return MMCMC_OK;
-        }
-        const size_t D = (size_t)dim;
-        std::vector<TT> h(2 * D);
-        for (size_t i = 0; i < D; ++i) {
-            h[i] = (TT)scale[i];
-            h[D + i] = TT(1) / h[i]; /* r_i, in the tensor type: what the stop criterion multiplies with */
-            if (!std::isfinite(scale[i]) || !(scale[i] > 0.0) || !std::isfinite(h[i]) || !(h[i] > TT(0)) || !std::isfinite(h[D + i]) || !(h[D + i] > TT(0)))
-                return MMCMC_ERR_INVALID_ARG;
-        }
-        if (dim > 32)
-            return MMCMC_ERR_UNSUPPORTED;
-        DevGuard g(device);
-        const mm_user_target *unit = metric_unit ? metric_unit : mm_rtc_metric_unit(kind, dim);
-        if (!unit)
-            return MMCMC_ERR_UNSUPPORTED; /* no run-time compiler (or the unit does not build): nothing changed */
-        MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
-        if (!metric_unit_verified(unit))
-            return MMCMC_ERR_UNSUPPORTED;
-        if (!d_metric) /* room for a dense metric's two packed factors too */
-            MM_HIP(hipMalloc((void **)&d_metric, 2 * mm_tri_len(D) * sizeof(TT)));
-        if (!d_metric_scratch) {
-            size_t stack = 0, tile = 0;
-            unit_sizes(D, &stack, &tile);
-            MM_HIP(hipMalloc((void **)&d_metric_scratch, (n_chains + 63) / 64 * stack));
-        }
-        MM_HIP(hipMemcpy(d_metric, h.data(), 2 * D * sizeof(TT), hipMemcpyHostToDevice));
-        metric_unit = unit;
-        metric.assign(scale, scale + D);
-        metric_chol.clear(); /* one metric per handle: a diagonal one replaces a dense one */
-        has_dense = false;
-        if (!has_metric) {
-            variant_before_metric = variant;
-            has_metric = true;
-        }
-        variant = 7;
-        return MMCMC_OK;
+        if (!dense)
+            return mm_diag_prepare<TT>(values, (size_t)dim, true, image);
+        std::vector<TT> li;
+        if (!mm_dense_prepare<TT>(values, (size_t)dim, image, li))
+            return false;
+        image.insert(image.end(), li.begin(), li.end());
+        return true;
     }
 
-    /* the same for a dense metric: chol = L row-major [dim, dim]; NULL removes whichever metric is set */
-    int set_metric_dense(const double *chol) override
+    /* mmcmc_nuts_set_metric (dense = false: values = the scales [dim]) and mmcmc_nuts_set_metric_dense (values = L row-major
+     * [dim, dim]): every value is checked before anything changes; NULL, through either, removes whichever metric is set and
+     * gives the handle its variant back */
+    int set_metric(bool dense, const double *values) override
     {
-        if (!chol)
-            return set_metric(nullptr);
-        if (dim < 1)
+        if (!values) {
+            met.clear(variant);
+            return MMCMC_OK;
+        }
+        if (dense && dim < 1)
             return MMCMC_ERR_INVALID_ARG;
         const size_t D = (size_t)dim;
-        std::vector<TT> l, li;
-        if (!mm_dense_prepare<TT>(chol, D, l, li))
+        std::vector<TT> image;
+        if (!metric_image(dense, values, image))
             return MMCMC_ERR_INVALID_ARG;
         if (dim > 32)
             return MMCMC_ERR_UNSUPPORTED;
         DevGuard g(device);
-        const mm_user_target *unit = dense_unit ? dense_unit : mm_rtc_dense_metric_unit(kind, dim);
+        const mm_user_target *&kept = dense ? dense_unit : metric_unit;
+        const mm_user_target *unit = kept ? kept : mm_rtc_metric_unit(kind, dim, dense);
         if (!unit)
             return MMCMC_ERR_UNSUPPORTED; /* no run-time compiler (or the unit does not build): nothing changed */
         MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
-        if (!metric_unit_verified(unit, true))
+        if (!metric_unit_verified(unit, dense))
             return MMCMC_ERR_UNSUPPORTED;
-        if (!d_metric)
+        if (!d_metric) /* room for either kind: a dense metric's two packed factors */
             MM_HIP(hipMalloc((void **)&d_metric, 2 * mm_tri_len(D) * sizeof(TT)));
         if (!d_metric_scratch) {
             size_t stack = 0, tile = 0;
             unit_sizes(D, &stack, &tile);
             MM_HIP(hipMalloc((void **)&d_metric_scratch, (n_chains + 63) / 64 * stack));
         }
-        MM_HIP(hipMemcpy(d_metric, l.data(), l.size() * sizeof(TT), hipMemcpyHostToDevice));
-        MM_HIP(hipMemcpy(d_metric + l.size(), li.data(), li.size() * sizeof(TT), hipMemcpyHostToDevice));
-        dense_unit = unit;
-        metric_chol.assign(chol, chol + D * D);
-        metric.assign(D, 0.0); /* what mmcmc_nuts_metric reports: the marginal standard deviations, the row norms of L */
-        for (size_t i = 0; i < D; ++i) {
-            double q = 0.0;
-            for (size_t j = 0; j <= i; ++j)
-                q += chol[i * D + j] * chol[i * D + j];
-            metric[i] = std::sqrt(q);
-        }
-        if (!has_metric) {
-            variant_before_metric = variant;
-            has_metric = true;
-        }
-        has_dense = true;
-        variant = 7;
+        MM_HIP(hipMemcpy(d_metric, image.data(), image.size() * sizeof(TT), hipMemcpyHostToDevice));
+        kept = unit;
+        if (dense)
+            met.commit_dense(values, D, variant);
+        else
+            met.commit_diag(values, D, variant);
         return MMCMC_OK;
     }
 
@@ -554,7 +487,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
 
     int set_variant(int v) override
     {
-        if (has_metric) /* only the metric unit has kernels that read a metric: it is variant 7 until the metric is cleared */
+        if (met.kind != MM_METRIC_NONE) /* only the metric unit has kernels that read a metric: it is variant 7 until the metric is cleared */
             return v == 7 ? MMCMC_OK : (v >= 0 && v <= 7) ? MMCMC_ERR_UNSUPPORTED : MMCMC_ERR_INVALID_ARG;
         if ((v == 0 && k) || (v >= 1 && v <= 3 && lg) || (v == 4 && k && k->run_async) || (v == 5 && k && k->run_pair) ||
             (v == 6 && generic_ok) || (v == 7 && user)) {
@@ -860,6 +793,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
         const int type_mode = std::is_same<TT, double>::value ? 2 : (std::is_same<ST, double>::value ? 0 : 1);
         const unsigned int grid64 = (unsigned int)((n_chains + 63) / 64);
         hipError_t e;
+        const bool has_metric = met.kind != MM_METRIC_NONE, has_dense = met.kind == MM_METRIC_DENSE;
         const bool rtc_target = (user && variant == 7) || has_metric; /* kernels of a run-time compiled unit */
         if (rtc_target) {
             mm_nuts_init_args<TT, ST> ia;
@@ -1263,25 +1197,13 @@ int mmcmc_nuts_adapt_state(mmcmc_nuts *h, double *out)
 {
     return (h && out) ? h->p->adapt_state(out) : MMCMC_ERR_INVALID_ARG;
 }
-int mmcmc_nuts_set_metric(mmcmc_nuts *h, const double *scale) { return h ? h->p->set_metric(scale) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_nuts_set_metric(mmcmc_nuts *h, const double *scale) { return h ? h->p->set_metric(false, scale) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_nuts_metric(mmcmc_nuts *h, double *scale_out)
 {
-    if (!h || !scale_out)
-        return MMCMC_ERR_INVALID_ARG;
-    for (int i = 0; i < h->p->dim; ++i)
-        scale_out[i] = h->p->has_metric ? h->p->metric[(size_t)i] : 1.0;
-    return h->p->has_dense ? 2 : h->p->has_metric ? 1 : 0;
+    return h && scale_out ? h->p->met.report_scale(scale_out, (size_t)h->p->dim) : MMCMC_ERR_INVALID_ARG;
 }
-int mmcmc_nuts_set_metric_dense(mmcmc_nuts *h, const double *chol) { return h ? h->p->set_metric_dense(chol) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_nuts_metric_dense(mmcmc_nuts *h, double *chol_out)
-{
-    if (!h || !chol_out)
-        return MMCMC_ERR_INVALID_ARG;
-    if (!h->p->has_dense)
-        return 0;
-    std::copy(h->p->metric_chol.begin(), h->p->metric_chol.end(), chol_out);
-    return 1;
-}
+int mmcmc_nuts_set_metric_dense(mmcmc_nuts *h, const double *chol) { return h ? h->p->set_metric(true, chol) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_nuts_metric_dense(mmcmc_nuts *h, double *chol_out) { return h && chol_out ? h->p->met.report_chol(chol_out) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_nuts_set_state(mmcmc_nuts *h, const void *x, int is_device, void *stream)
 {
     return (h && x) ? h->p->set_state(x, is_device, stream) : MMCMC_ERR_INVALID_ARG;

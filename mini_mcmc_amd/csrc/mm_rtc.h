@@ -29,11 +29,11 @@ const mm_user_target *mm_rtc_builtin_nuts(int kind, int dim); /* the same for NU
 /* the metric unit of a target kind (built-in, or a caller's plain / autodiff / data kind) at dim <= 32, built on the first
  * set_metric: its HMC kernels answer mm_rtc_launch_run(sampler 1) with a mm_run_metric_args<T> block, its NUTS kernels
  * mm_rtc_launch_nuts with mm_nuts_init_metric_args / mm_nuts_metric_args (init 1 / 0 lanes in step / 2 pairs).  NULL: no
- * run-time compiler, no gradient functor behind the kind, or the unit failed to build */
-const mm_user_target *mm_rtc_metric_unit(int kind, int dim);
-/* the dense-metric unit of the same kinds, a unit of its own built on the first set_metric_dense: the same launchers, the
- * argument blocks mm_run_dense_args<T> / mm_nuts_init_dense_args / mm_nuts_dense_args (the factors' pointers at the end) */
-const mm_user_target *mm_rtc_dense_metric_unit(int kind, int dim);
+ * run-time compiler, no gradient functor behind the kind, or the unit failed to build.
+ * dense: the dense-metric unit of the same kinds (the kernel headers' and mm_path.h's "mm_rtc_dense_metric_unit"), a unit of
+ * its own built on the first set_metric_dense: the same launchers, the argument blocks mm_run_dense_args<T> /
+ * mm_nuts_init_dense_args / mm_nuts_dense_args (the factors' pointers at the end) */
+const mm_user_target *mm_rtc_metric_unit(int kind, int dim, bool dense);
 hipError_t mm_rtc_launch_discrete(const mm_user_target *t, void *args, size_t args_bytes, unsigned int grid, hipStream_t stream);
 /* kernels of a registered target: sampler 0 MH / 1 HMC, dtype 0 f32 / 1 f64; `args` = the mm_run_args<T> block */
 hipError_t mm_rtc_launch_run_split(const mm_user_target *t, int sampler, void *args, size_t args_bytes, unsigned int grid, size_t lds,

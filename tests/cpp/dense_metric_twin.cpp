@@ -2,7 +2,7 @@
  *
  * A plain C++17 program around the very headers the kernels are compiled from, built with the flags of oracle/Makefile
  * (-ffp-contract=off), so what it computes is what the device computes, bit for bit.  The factors come from
- * csrc/mm_dense_host.h, which the library's setters use too.  The runners (run_hmc, run_nuts, start, ...) are those of the
+ * csrc/mm_metric_host.h, which the library's setters use too.  The runners (run_hmc, run_nuts, start, ...) are those of the
  * diagonal metric's twin, metric_twin.cpp, included below with its main() renamed: they take the metric as a type.
  *
  * Without arguments it checks, at dims 2 (Gaussian2D), 3, 9 and 32 (RosenbrockND), HMC in f32 and f64 with L in {1, 7} and NUTS
@@ -21,7 +21,7 @@
 #include "metric_twin.cpp"
 #undef main
 
-#include "../../mini_mcmc_amd/csrc/mm_dense_host.h"
+#include "../../mini_mcmc_amd/csrc/mm_metric_host.h"
 
 /* the two packed factors, each in a heap block of exactly D (D + 1) / 2 elements, and the metric that points at them */
 template <class T, int D> struct dense_factors {

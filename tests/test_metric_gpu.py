@@ -238,6 +238,32 @@ def test_bad_values_and_unsupported_handles_change_nothing():
         h.close()
 
 
+def test_a_scale_without_an_f32_reciprocal_is_hmcs_to_take_and_nuts_to_refuse():
+    """The one respect in which the two diagonal checks differ (csrc/mm_metric_host.h: mm_diag_prepare): 1e-39 is finite and
+    > 0 as f32, 1 / 1e-39 is not.  HMC never forms r_i = 1 / s_i; NUTS's stop criterion multiplies by it.  Neither handle is
+    run with that metric."""
+    from mini_mcmc_amd import _lib as L
+    from mini_mcmc_amd.core import init_with_seed
+    from mini_mcmc_amd.distributions import RosenbrockND
+    from mini_mcmc_amd.hmc import HMC
+    from mini_mcmc_amd.nuts import NUTS
+
+    lib = L.lib()
+    x0 = init_with_seed(65, 3, 42)
+    tiny, good = np.array([1.0, 1e-39, 1.0]), np.array([0.5, 2.0, 3.0])
+    p_tiny = tiny.ctypes.data_as(C.POINTER(C.c_double))
+    out = (C.c_double * 3)()
+    h = HMC(RosenbrockND(3), x0.astype(np.float32), 0.03, 5)
+    assert lib.mmcmc_hmc_set_metric(h._h, p_tiny) == L.OK
+    assert lib.mmcmc_hmc_metric(h._h, out) == 1 and list(out) == list(tiny)
+    h.close()
+    n = NUTS(RosenbrockND(3), x0, 0.8, mode=0)  # tensor type f32
+    n.metric = good
+    assert lib.mmcmc_nuts_set_metric(n._h, p_tiny) == L.ERR_INVALID_ARG
+    assert lib.mmcmc_nuts_metric(n._h, out) == 1 and list(out) == list(good) and n.kernel_variant == 7
+    n.close()
+
+
 def test_lane_group_handle_moves_to_the_unit_and_back():
     from mini_mcmc_amd.core import init_with_seed
     from mini_mcmc_amd.distributions import GaussianND

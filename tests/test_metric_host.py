@@ -5,15 +5,19 @@
     undefined-behaviour sanitizers (a stand-alone program: no preload involved);
   * an independent float64 restatement in numpy of diagonal-metric HMC, with the half-kicks kept apart as hmc.rs:403-429
     writes them, on the noise the twin prints;
+  * tests/cpp/metric_host.cpp -- csrc/mm_metric_host.h on its own: the diagonal checks with the device image they produce,
+    and the record of the metric both handle types keep --, likewise plain and under the sanitizers;
   * the four entry points refuse a NULL handle;
   * warmup.estimate_scale against numpy float64."""
 import ctypes as C
+import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import autodiff_common as A
 import metric_common as M
 
 
@@ -29,6 +33,37 @@ def test_twin_ones_metric_is_no_metric_and_power_of_two_identity(tmp_path_factor
     assert failed == 0
     # not vacuous: (a) 2 targets x 3 L x 2 + 3 modes x 5; (b) 4 dims x (2 dtypes x 3 L x 2 + 3 modes x 2 x 2)
     assert checks == 2 * 3 * 2 + 3 * 5 + 4 * (2 * 3 * 2 + 3 * 2 * 2)
+
+
+def test_metric_host_header_is_host_only():
+    text = open(os.path.join(M.ROOT, "mini_mcmc_amd", "csrc", "mm_metric_host.h")).read()
+    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', text) == ["cmath", "cstddef", "vector"]
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_diagonal_checks_and_the_metric_record_on_the_host(tmp_path, sanitize):
+    """tests/cpp/metric_host.cpp (its head comment), plain host code with its own main: as built and once more linked with
+    the address and undefined-behaviour sanitizers' runtimes, no preload involved"""
+    cxx, flags = A.host_flags()
+    exe = str(tmp_path / "metric_host")
+    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
+    r = subprocess.run([cxx] + flags + extra + [os.path.join(M.ROOT, "tests", "cpp", "metric_host.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0, (r.returncode, r.stdout[-3000:], r.stderr[-4000:])
+    m = re.search(r"checks (\d+) failed (\d+)", r.stdout)
+    assert m, r.stdout[-1000:]
+    checks, failed = map(int, m.groups())
+    assert failed == 0
+    # not vacuous.  mm_diag_prepare: placements = the positions of D = 1 and D = 3; two forms (without / with the inverse)
+    accepted, placements, forms = 5, 1 + 3, 2
+    bad = {"float": 6 + 2, "double": 6}  # NaN, +inf, -inf, 0, -0.0, -1; as float also 1e-60 and 1e60
+    diag = sum(accepted * 2 * forms + n * placements * forms + 2 * placements for n in bad.values())
+    # the record: 2 starting variants, every sequence of 1 .. 3 out of 5 operations, 4 checks after each operation
+    record = 2 * 4 * sum(length * 5 ** length for length in (1, 2, 3))
+    assert checks == diag + record
 
 
 def test_float64_restatement_of_diagonal_metric_hmc_on_the_twins_noise(tmp_path_factory, tmp_path):
