@@ -25,6 +25,7 @@
 #include "../../include/mmcmc.h"
 #include "mm_host.h"
 #include "mm_stats_fft.h"
+#include "mm_stats_plan.h"
 #include "mm_tuning.h"
 
 #include <hip/hip_runtime.h>
@@ -1538,15 +1539,6 @@ __global__ __launch_bounds__(256) void mm_fft_finish_kernel(const float *__restr
     }
 }
 
-/* tiles of 8 time steps x 16 lags of one parameter's (t, lag) triangle (the kernel's own count) */
-static unsigned int stats_tile_count(size_t m)
-{
-    unsigned int n = 0;
-    for (size_t kb = 0; 16 * kb < m; ++kb)
-        n += (unsigned int)((m - 16 * kb + 7) / 8);
-    return n;
-}
-
 /* The tail of the statistics, one launch, two kinds of blocks.
  *
  * Blocks [0, nb_red): out[lag, d] = sum over waves of slabs[w, d, lag].  One wave per group of 64 outputs would
@@ -1670,106 +1662,10 @@ __global__ void mm_parts_sum_kernel(const float *__restrict__ parts, unsigned in
 
 } // namespace
 
-/* number of waves (= per-wave lag-sum slabs) the half-chain kernel is launched with */
-static unsigned int stats_n_slabs(size_t n_chains)
-{
-    /* 4 waves per SIMD hide the LDS / global latencies of the half-chain loop; more only lengthens the slab reduction
-     * (measured at [65536, 400, 3]: 1024 waves 1.65 ms, 2048 0.96, 4096 0.69 + 0.08, 8192 0.82 + 0.21) */
-    const char *e = mm_tuning_env("MMCMC_STATS_WAVES");
-    const size_t w = e ? (size_t)atoi(e) : 4096;
-    return (unsigned int)std::min<size_t>(2 * n_chains, w ? w : 4096);
-}
-
 /* ---- which kernel reduces a sample: mmcmc_stats_set_kernel (include/mmcmc.h) ---- */
 static std::atomic<int> g_stats_kernel{MMCMC_STATS_KERNEL_AUTO};
 /* lag products (chains x dim x (n / 2)^2) the O(m^2) from-global-memory path may be asked for; 0 = no limit */
 static std::atomic<uint64_t> g_stats_direct_work_limit{1ull << 46};
-
-/* the power-spectrum path (mm_chain_fft_kernel): half-chains longer than 100 draws, as stats.rs:549 switches */
-struct StatsFftPlan {
-    bool use = false;
-    int r1 = 0, dt = 0, wpe = 0;
-    unsigned int n_pt = 0, n_wg = 0, N = 0;
-};
-
-/* sel < 0: read the process-wide selector; the workspace is sized with sel = MMCMC_STATS_KERNEL_FFT (and for the direct
- * kernels as well), so that a mmcmc_stats_set_kernel() from another thread between the sizing and the launch of one call
- * can change which kernel runs but never make the buffer too small */
-static StatsFftPlan stats_fft_plan(size_t n_chains, size_t n, size_t dim, int device, int sel_in = -1)
-{
-    StatsFftPlan p;
-    const size_t m = n / 2;
-    const int sel = sel_in >= 0 ? sel_in : g_stats_kernel.load(std::memory_order_relaxed);
-    if (sel != MMCMC_STATS_KERNEL_AUTO && sel != MMCMC_STATS_KERNEL_FFT)
-        return p;
-    if (m > 1024 || m < 2 || (sel == MMCMC_STATS_KERNEL_AUTO && m <= 100))
-        return p;
-    p.use = true;
-    p.r1 = m <= 256 ? 8 : m <= 512 ? 16 : 32;
-    p.N = 64u * (unsigned int)p.r1;
-    /* parameters per wave: as many as the registers hold without spilling (R1 = 8: 4 at two waves per SIMD, 3 at three;
-     * R1 = 16: 3; R1 = 32: 1), the tiles of a larger dimension as even as possible */
-    const size_t dt_max = p.r1 == 8 ? 4 : p.r1 == 16 ? 3 : 1;
-    p.n_pt = (unsigned int)((dim + dt_max - 1) / dt_max);
-    p.dt = (int)((dim + p.n_pt - 1) / p.n_pt);
-    p.wpe = p.r1 == 8 && p.dt <= 3 ? 3 : 2;
-    /* resident workgroups of four waves: waves per SIMD x CUs, shared between the parameter tiles */
-    /* the workgroup count fixes which chains a wave sums in f32, so it must not depend on the device (CU count, partition
-     * mode): 256 compute units' worth, an MI355X's, on every device -- R-hat / ESS are then the same bits everywhere */
-    (void)device;
-    const unsigned int wpe = (unsigned int)p.wpe;
-    const unsigned int resident = 256u * wpe;
-    p.n_wg = std::max(1u, resident / p.n_pt);
-    if (const char *e = mm_tuning_env("MMCMC_FFT_NWG_MULT")) /* workgroups per resident slot (percent) */
-        p.n_wg = std::max(1u, (unsigned int)((unsigned long long)p.n_wg * (unsigned int)atoi(e) / 100u));
-    p.n_wg = (unsigned int)std::min<size_t>(p.n_wg, (n_chains + 3) / 4);
-    return p;
-}
-
-/* the long-chain paths: half-chains of 1025 .. 2048 draws (mm_chain_fft_long_kernel, N1 = 2) and beyond (mm_chain_fft_res_kernel) */
-struct StatsLongPlan {
-    bool use = false;
-    bool res = false; /* round 6: one (residue, parameter) per wave, spectrum in registers (mm_chain_fft_res_kernel): N1 >= 3 */
-    unsigned int N1 = 0, N = 0, n_wg = 0;
-};
-constexpr size_t kStatsLongMaxM = 131072; /* N = 2^18: the inverse (mm_fft_finish_long_kernel) is O(m N) per parameter */
-/* LDS of a workgroup of mm_chain_fft_long_kernel: the spectrum S[4096] and the wave's exchange block */
-constexpr size_t kStatsLongLds = ((size_t)4096 + 2 * (size_t)mm_fft_plan<32>::LDS_CX) * sizeof(float);
-static_assert(kStatsLongLds <= 64 * 1024, "mm_chain_fft_long_kernel is launched without raising its dynamic LDS limit");
-static StatsLongPlan stats_long_plan(size_t n_chains, size_t n, size_t dim, int sel_in = -1)
-{
-    StatsLongPlan p;
-    const size_t m = n / 2;
-    const int sel = sel_in >= 0 ? sel_in : g_stats_kernel.load(std::memory_order_relaxed);
-    if ((sel != MMCMC_STATS_KERNEL_AUTO && sel != MMCMC_STATS_KERNEL_FFT) || m <= 1024 || m > kStatsLongMaxM)
-        return p;
-    p.use = true;
-    /* N = 2048 N1 >= 2 m, N1 the SMALLEST such count (round 6, late: it was the next power of two -- but a residue wave reads
-     * the whole chain, so time goes as N1 x the data: m = 10 000 took N1 = 16 where 10 do, [16384, 20000, 3] 20.7 -> 9.0 ms, [16384, 40000, 3] 73 -> 31.7) */
-    p.N1 = (unsigned int)std::max<size_t>(2, (m + 1023) / 1024);
-    p.N = 2048u * p.N1;
-    if (p.N1 >= 3) {
-        /* chain groups: as many as keep ONE resident round of one-wave workgroups busy -- one per SIMD by their registers, 1024
-         * on an MI355X; the figure is a constant, not a device query, because the group count fixes the f32 summation grouping
-         * -- in multiples of 8 (the kernel's XCD mapping), at most 512 */
-        p.res = true;
-        /* inner transforms of 2048 points, one wave per SIMD: N1 residues per parameter */
-        const size_t per = dim * p.N1;
-        size_t g = per > 0 ? 1024 / per : 8;
-        g = std::min<size_t>(512, std::max<size_t>(8, g / 8 * 8));
-        p.n_wg = (unsigned int)std::min<size_t>(g, n_chains);
-        return p;
-    }
-    /* device-independent (the workgroup count fixes the f32 summation grouping): at most 512 chain groups, and no more than fit
-     * the one-wave workgroups an MI355X holds at once with this kernel's LDS (1024 at N1 = 2: a launch of 1536 ran a second,
-     * half-empty round), a multiple of 8 (the kernel's XCD mapping); fewer for few chains */
-    const size_t resident = 256 * std::max<size_t>(1, (160u << 10) / kStatsLongLds); /* MI355X: 256 CUs x workgroups per CU by their LDS */
-    size_t g = 512;
-    if (dim > 0 && g * dim > resident)
-        g = std::max<size_t>(8, resident / dim / 8 * 8);
-    p.n_wg = (unsigned int)std::min<size_t>(g, n_chains);
-    return p;
-}
 
 /* w_N^j = exp(-2 pi i j / N), j < N, as f32 pairs, then cos(2 pi j / N) as f64: one table per device and N1, never freed
  * (32 KB x N1; a process that used every N1 = 2 .. 128 once holds 260 MB of them per device) */
@@ -1852,36 +1748,62 @@ static const mm_cx *stats_fft_twiddles(int device, int r1)
     return d;
 }
 
-template <class T, int R1, int DT, int WPE, bool TOP>
-static int stats_fft_launch1(const StatsFftPlan &p, const void *sample, size_t n_chains, size_t n, size_t dim, size_t m,
-                             const mm_cx *tw, float *means, float *ssq, float *slabs, hipStream_t stream)
+/* the same test for mm_rank.hip, whose entry points run mmcmc_split_rhat_mean_ess on arrays of the sample's shape (mm_rank.h) */
+bool mm_stats_shape_fits(size_t n, size_t dim)
 {
-    const size_t lds = (size_t)4 * mm_fft_plan<R1>::LDS_CX * sizeof(mm_cx);
-    if (lds > 64 * 1024) {
+    return stats_bins_fit(n, dim);
+}
+
+static_assert(kStatsWbChunks == MM_WB_CHUNKS, "mm_stats_plan.h sizes the tail kernel's grid");
+static_assert(mm_fft_plan<8>::LDS_CX == 8 * kStatsFftLdsCx && mm_fft_plan<32>::LDS_CX == 32 * kStatsFftLdsCx &&
+                  sizeof(mm_cx) == 2 * sizeof(float),
+              "mm_stats_plan.h sizes the transform kernels' LDS");
+
+/* the measurement knobs of mm_stats_plan.h (mm_tuning.h: a shipped library reads no environment) */
+static mm_stats_knobs stats_knobs()
+{
+    const char *mult = mm_tuning_env("MMCMC_FFT_NWG_MULT"), *waves = mm_tuning_env("MMCMC_STATS_WAVES");
+    const int w = waves ? atoi(waves) : 0; /* set to 0: set, and the default count */
+    return mm_stats_knobs{mult ? atoi(mult) : 100, waves && !w ? 4096 : w};
+}
+
+template <int V>
+using StatsInt = std::integral_constant<int, V>;
+
+/* what every first-stage kernel is given, in its parameters' types */
+struct StatsCall {
+    const void *sample;
+    unsigned long long n_chains;
+    unsigned int n, dim, m;
+    float *means, *ssq, *slabs;
+    hipStream_t stream;
+};
+
+template <class T, int R1, int DT, int WPE, bool TOP>
+static int stats_fft_launch1(const mm_stats_plan &p, const StatsCall &c, const mm_cx *tw)
+{
+    if (p.raise_lds) {
         static std::atomic<unsigned long long> attr_set{0};
         int dev = 0;
         (void)hipGetDevice(&dev);
         if (!(attr_set.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
             MM_HIP(hipFuncSetAttribute((const void *)mm_chain_fft_kernel<T, R1, DT, WPE, TOP>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.first.lds));
             attr_set.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
         }
     }
-    hipLaunchKernelGGL((mm_chain_fft_kernel<T, R1, DT, WPE, TOP>), dim3(p.n_wg * p.n_pt), dim3(256), lds, stream,
-                       (const T *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim,
-                       (unsigned int)m, p.n_pt, tw, means, ssq, slabs);
+    hipLaunchKernelGGL((mm_chain_fft_kernel<T, R1, DT, WPE, TOP>), dim3(p.first.gx), dim3(p.first.block), p.first.lds, c.stream,
+                       (const T *)c.sample, c.n_chains, c.n, c.dim, c.m, p.arg, tw, c.means, c.ssq, c.slabs);
     return MMCMC_OK;
 }
 
+/* the instantiated (R1, DT, WPE) of mm_chain_fft_kernel: every triple stats_fft_geom gives (tests/cpp/stats_plan.cpp) */
 template <class T>
-static int stats_fft_launch(const StatsFftPlan &p, const void *sample, size_t n_chains, size_t n, size_t dim, size_t m,
-                            const mm_cx *tw, float *means, float *ssq, float *slabs, hipStream_t stream)
+static int stats_fft_launch(const mm_stats_plan &p, const StatsCall &c, const mm_cx *tw)
 {
-    const bool top = m > 64 * (size_t)(p.r1 / 2 - 1); /* only a lane's last point can be padding */
 #define MM_FFT_CASE(R1V, DTV, WPEV)                                                                                 \
     if (p.r1 == R1V && p.dt == DTV && p.wpe == WPEV)                                                                \
-    return top ? stats_fft_launch1<T, R1V, DTV, WPEV, true>(p, sample, n_chains, n, dim, m, tw, means, ssq, slabs, stream) \
-               : stats_fft_launch1<T, R1V, DTV, WPEV, false>(p, sample, n_chains, n, dim, m, tw, means, ssq, slabs, stream)
+    return p.top ? stats_fft_launch1<T, R1V, DTV, WPEV, true>(p, c, tw) : stats_fft_launch1<T, R1V, DTV, WPEV, false>(p, c, tw)
     MM_FFT_CASE(8, 1, 3);
     MM_FFT_CASE(8, 2, 3);
     MM_FFT_CASE(8, 3, 3);
@@ -1894,326 +1816,137 @@ static int stats_fft_launch(const StatsFftPlan &p, const void *sample, size_t n_
     return MMCMC_ERR_UNSUPPORTED;
 }
 
-/* The transform paths count bins (dim x N, N = 2048 N1 up to 2^18 beyond 1024 draws per half-chain) in 32 bits: a shape
- * whose count would wrap is refused from the shape alone, whichever kernel is selected, before anything is allocated */
-static bool stats_bins_fit(size_t n, size_t dim)
+/* The first-stage kernels of plan `p` for element type T: per-workgroup rows (lag sums, or power-spectrum bins) into c.slabs,
+ * the half-chains' means and centred sums of squares into c.means / c.ssq */
+template <class T>
+static int stats_first_stage(const mm_stats_plan &p, const StatsCall &c, const mm_cx *tw, const mm_cx *wN)
 {
-    const size_t m = n / 2;
-    if (m <= 1024 || m > kStatsLongMaxM)
-        return true; /* one wave-level transform (N <= 2048, dim < 2^16) or no transform at all */
-    const uint64_t N = 2048ull * std::max<uint64_t>(2, (m + 1023) / 1024);
-    return (uint64_t)dim * N < (1ull << 32);
+    const T *sample = (const T *)c.sample;
+    const dim3 grid(p.first.gx, p.first.gy, p.first.gz), block(p.first.block);
+    const size_t lds = p.first.lds;
+    switch (p.path) {
+    case MM_STATS_FFT:
+        return stats_fft_launch<T>(p, c, tw);
+    case MM_STATS_FFT_LONG:
+        hipLaunchKernelGGL(mm_chain_fft_long_kernel<T>, grid, block, lds, c.stream, sample, c.n_chains, c.n, c.dim, c.m, p.rows, tw,
+                           wN, c.means, c.ssq, c.slabs);
+        break;
+    case MM_STATS_FFT_RES:
+        if (p.moments)
+            hipLaunchKernelGGL(mm_half_chain_moments_any_kernel<T>, dim3(p.pre.gx), dim3(p.pre.block), 0, c.stream, sample,
+                               c.n_chains, c.n, c.dim, c.m, c.means, c.ssq);
+        else
+            hipLaunchKernelGGL(mm_half_chain_means_kernel<T>, dim3(p.pre.gx), dim3(p.pre.block), 0, c.stream, sample, c.n_chains,
+                               c.n, c.dim, c.m, c.means);
+        hipLaunchKernelGGL((mm_chain_fft_res_kernel<T, 32, 2, 1>), grid, block, lds, c.stream, sample, c.n_chains, c.n, c.dim, c.m,
+                           p.arg, p.rows, tw, wN, c.means, c.ssq, c.slabs);
+        break;
+    case MM_STATS_TILE1: {
+        auto go = [&](auto tpl, auto npre) {
+            hipLaunchKernelGGL((mm_half_chain_tile1_kernel<T, decltype(tpl)::value, decltype(npre)::value>), grid, block, lds,
+                               c.stream, sample, c.n_chains, c.n, c.dim, c.m, p.arg, c.means, c.ssq, c.slabs);
+        };
+        if (p.npre == 8)
+            go(StatsInt<3>{}, StatsInt<8>{});
+        else if (p.tpl == 1)
+            go(StatsInt<1>{}, StatsInt<4>{});
+        else if (p.tpl == 2)
+            go(StatsInt<2>{}, StatsInt<4>{});
+        else
+            go(StatsInt<3>{}, StatsInt<4>{});
+        break;
+    }
+    case MM_STATS_TILE: {
+        auto go = [&](auto tpl) {
+            if constexpr (std::is_same<T, float>::value) /* 16-byte loads exist for f32 alone */
+                if (p.vec) {
+                    hipLaunchKernelGGL((mm_half_chain_tile_kernel<float, decltype(tpl)::value, true>), grid, block, lds, c.stream,
+                                       sample, c.n_chains, c.n, c.dim, c.m, c.means, c.ssq, c.slabs);
+                    return;
+                }
+            hipLaunchKernelGGL((mm_half_chain_tile_kernel<T, decltype(tpl)::value, false>), grid, block, lds, c.stream, sample,
+                               c.n_chains, c.n, c.dim, c.m, c.means, c.ssq, c.slabs);
+        };
+        if (p.tpl == 2)
+            go(StatsInt<2>{});
+        else if (p.tpl == 4)
+            go(StatsInt<4>{});
+        else
+            go(StatsInt<8>{});
+        break;
+    }
+    case MM_STATS_MFMA:
+        hipLaunchKernelGGL(mm_half_chain_mfma_kernel<T>, grid, block, lds, c.stream, sample, c.n_chains, c.n, c.dim, c.m, p.arg,
+                           c.means, c.ssq, c.slabs);
+        break;
+    case MM_STATS_LDS:
+        if (p.raise_lds)
+            MM_HIP(hipFuncSetAttribute((const void *)mm_half_chain_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(mm_half_chain_kernel<T>, grid, block, lds, c.stream, sample, c.n_chains, c.n, c.dim, c.m, p.arg, c.means,
+                           c.ssq, c.slabs);
+        break;
+    case MM_STATS_ANY:
+        hipLaunchKernelGGL(mm_half_chain_moments_any_kernel<T>, dim3(p.pre.gx), dim3(p.pre.block), 0, c.stream, sample, c.n_chains,
+                           c.n, c.dim, c.m, c.means, c.ssq);
+        hipLaunchKernelGGL(mm_lag_sums_any_kernel<T>, grid, block, lds, c.stream, sample, c.n_chains, c.n, c.dim, c.m, c.means,
+                           p.rows, c.slabs);
+        break;
+    }
+    return MMCMC_OK;
 }
 
-/* the same test for mm_rank.hip, whose entry points run mmcmc_split_rhat_mean_ess on arrays of the sample's shape (mm_rank.h) */
-bool mm_stats_shape_fits(size_t n, size_t dim)
+/* The sufficient statistics of `sample` by the kernels of one mm_stats_plan: means, ssq [2 n_chains, dim], and the lag sums --
+ * *wrote_total: as one total [m, dim] in `total`; otherwise as n_parts partial totals in `partials`, for the caller to add
+ * up in order.  wb_part: NULL, or [dim][MM_WB_CHUNKS][3] doubles for the cross-chain sums (single-GPU path).  slabs_ws: NULL,
+ * or device memory of mm_stats_ws_floats floats. */
+static int stats_partials_impl(const void *sample, int dtype, size_t n_chains, size_t n, size_t dim, float *means, float *ssq,
+                               float *partials, float *total, double *wb_part, float *slabs_ws, unsigned int n_parts, int device,
+                               void *stream_v, bool *wrote_total)
 {
-    return stats_bins_fit(n, dim);
-}
-
-/* floats of device workspace stats_partials_impl wants behind `slabs_ws` */
-static size_t stats_ws_floats(size_t n_chains, size_t n, size_t dim, unsigned int n_parts, int device)
-{
-    const size_t m = n / 2;
-    size_t need = (size_t)stats_n_slabs(n_chains) * dim * m;
-    const StatsFftPlan p = stats_fft_plan(n_chains, n, dim, device, MMCMC_STATS_KERNEL_FFT); /* whichever kernel runs */
-    if (p.use)
-        need = std::max(need, ((size_t)p.n_wg + n_parts) * dim * p.N);
-    const StatsLongPlan lp = stats_long_plan(n_chains, n, dim, MMCMC_STATS_KERNEL_FFT);
-    if (lp.use) /* slabs | partial totals | their f64 sum */
-        need = std::max(need, ((size_t)lp.n_wg + n_parts + 2) * dim * lp.N);
-    return need;
-}
-
-/* wb_part: NULL, or [dim][MM_WB_CHUNKS][3] doubles for the cross-chain sums (single-GPU path) */
-static int stats_partials_impl(const void *sample, int dtype, size_t n_chains, size_t n, size_t dim, float *means,
-                               float *ssq, float *acov_sum, double *wb_part, float *slabs_ws, unsigned int n_parts,
-                               int device, void *stream_v, unsigned int *parts_out, float *final_out = nullptr)
-{
-    /* final_out (may be NULL): where a path that produces the total itself writes it; *parts_out = 0 then */
-    if (parts_out)
-        *parts_out = n_parts;
-    if (!sample || !means || !ssq || !acov_sum || n_chains == 0 || dim == 0 ||
-        (dtype != MMCMC_F32 && dtype != MMCMC_F64))
+    if (!sample || !means || !ssq || !partials || !total || !wrote_total)
         return MMCMC_ERR_INVALID_ARG;
-    const size_t m = n / 2;
-    if (m < 1 || n >= (1ull << 31) || dim >= (1u << 16) || !stats_bins_fit(n, dim))
-        return MMCMC_ERR_SHAPE;
-    int st = mm_check_device(device);
+    DevGuard g(device); /* which both entry points have checked */
+    hipStream_t stream = (hipStream_t)stream_v;
+    /* the one read of the selector: a racing mmcmc_stats_set_kernel picks one kernel or the other for the whole call */
+    const mm_stats_plan p = mm_stats_make_plan(n_chains, n, dim, dtype, g_stats_kernel.load(std::memory_order_relaxed), n_parts,
+                                               wb_part != nullptr, (uintptr_t)sample % 16 == 0, stats_knobs(),
+                                               g_stats_direct_work_limit.load(std::memory_order_relaxed));
+    if (p.status != MMCMC_OK) /* a bad count or element type, a shape no path takes, or one the chosen path refuses */
+        return p.status;
+    const bool finish = p.finish_kind != MM_STATS_FINISH_NONE, long_n = p.finish_kind == MM_STATS_FINISH_LONG;
+    const mm_cx *tw = finish ? stats_fft_twiddles(device, long_n ? 32 : p.r1) : nullptr;
+    const mm_cx *wN = long_n ? stats_long_tables(device, p.arg) : nullptr;
+    if ((finish && !tw) || (long_n && !wN))
+        return (int)hipErrorOutOfMemory;
+    float *ws = slabs_ws;
+    if (!ws)
+        MM_HIP(hipMallocAsync((void **)&ws, p.ws_floats * sizeof(float), stream));
+    float *bins = ws + p.off_bins;
+    const unsigned int m = (unsigned int)(n / 2);
+    const StatsCall c{sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, m, means, ssq, ws, stream};
+    const int st = dtype == MMCMC_F32 ? stats_first_stage<float>(p, c, tw, wN) : stats_first_stage<double>(p, c, tw, wN);
     if (st != MMCMC_OK)
         return st;
-    DevGuard g(device);
-    hipStream_t stream = (hipStream_t)stream_v;
-    const StatsFftPlan fp = stats_fft_plan(n_chains, n, dim, device);
-    if (fp.use) {
-        /* power spectrum per workgroup -> bin totals in n_parts partial sums (the tail kernel, with bins for lags) ->
-         * one inverse per parameter: acov_sum[0] is the total, *parts_out = 1 */
-        const mm_cx *tw = stats_fft_twiddles(device, fp.r1);
-        if (!tw)
-            return (int)hipErrorOutOfMemory;
-        const size_t slab_floats = (size_t)fp.n_wg * dim * fp.N, part_floats = (size_t)n_parts * dim * fp.N;
-        float *ws = slabs_ws;
-        if (!ws)
-            MM_HIP(hipMallocAsync((void **)&ws, (slab_floats + part_floats) * sizeof(float), stream));
-        float *bins = ws + slab_floats;
-        st = dtype == MMCMC_F32
-                 ? stats_fft_launch<float>(fp, sample, n_chains, n, dim, m, tw, means, ssq, ws, stream)
-                 : stats_fft_launch<double>(fp, sample, n_chains, n, dim, m, tw, means, ssq, ws, stream);
-        if (st != MMCMC_OK)
-            return st;
-        MM_HIP(hipGetLastError());
-        const unsigned int total_b = (unsigned int)(dim * fp.N);
-        const unsigned int nb_red = (total_b + 63) / 64 * n_parts, nb_wb = wb_part ? (unsigned int)dim * MM_WB_CHUNKS : 0u;
-        hipLaunchKernelGGL(mm_stats_tail_kernel, dim3(nb_red + nb_wb), dim3(256), 0, stream, ws, fp.n_wg,
-                           (unsigned int)dim, fp.N, bins, nb_red, n_parts, means, ssq,
-                           (unsigned long long)(2 * n_chains), (float)m, wb_part);
-        MM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(mm_fft_finish_kernel, dim3((unsigned int)dim * (unsigned int)((m + 31) / 32)), dim3(256),
-                           (2 * (size_t)fp.N + 256) * sizeof(double), stream, bins, n_parts, (unsigned int)dim, fp.N,
-                           (unsigned int)m, stats_fft_cos_table(tw, fp.r1), final_out ? final_out : acov_sum);
-        MM_HIP(hipGetLastError());
-        if (!slabs_ws)
-            MM_HIP(hipFreeAsync(ws, stream));
-        if (parts_out)
-            *parts_out = final_out ? 0 : 1;
-        return MMCMC_OK;
-    }
-    const StatsLongPlan lp = stats_long_plan(n_chains, n, dim);
-    if (lp.use) {
-        const mm_cx *tw = stats_fft_twiddles(device, 32), *wN = stats_long_tables(device, lp.N1);
-        if (!tw || !wN)
-            return (int)hipErrorOutOfMemory;
-        const size_t slab_floats = (size_t)lp.n_wg * dim * lp.N, part_floats = (size_t)n_parts * dim * lp.N,
-                     p_floats = 2 * (size_t)dim * lp.N;
-        float *ws = slabs_ws;
-        if (!ws)
-            MM_HIP(hipMallocAsync((void **)&ws, (slab_floats + part_floats + p_floats) * sizeof(float), stream));
-        float *bins = ws + slab_floats;
-        double *P = reinterpret_cast<double *>(ws + ((slab_floats + part_floats + 1) / 2) * 2);
-        const unsigned int grid = lp.n_wg * (unsigned int)dim;
-        if (lp.res) {
-            /* means by a streaming pass (dim <= 16: 64 dim threads per half-chain; wider samples through the any-length moments
-             * kernel), then one wave per (chain group, residue, parameter) */
-            const unsigned int n1r = lp.N1;
-            if ((uint64_t)2 * n_chains >= (1ull << 31) || (uint64_t)lp.n_wg * dim * n1r >= (1ull << 31))
-                return MMCMC_ERR_SHAPE;
-            const unsigned int g_mean = (unsigned int)(2 * n_chains), g_res = lp.n_wg * (unsigned int)dim * n1r;
-            const size_t lds_res = (size_t)mm_fft_plan<32>::LDS_CX * sizeof(mm_cx);
-#define MM_RES_LAUNCH(TT)                                                                                           \
-    do {                                                                                                            \
-        if (dim <= 16)                                                                                              \
-            hipLaunchKernelGGL(mm_half_chain_means_kernel<TT>, dim3(g_mean), dim3(64u * (unsigned int)dim), 0, stream, \
-                               (const TT *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, \
-                               (unsigned int)m, means);                                                             \
-        else                                                                                                        \
-            hipLaunchKernelGGL(mm_half_chain_moments_any_kernel<TT>, dim3(g_mean * (unsigned int)dim), dim3(64), 0, stream, \
-                               (const TT *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, \
-                               (unsigned int)m, means, ssq);                                                        \
-        hipLaunchKernelGGL((mm_chain_fft_res_kernel<TT, 32, 2, 1>), dim3(g_res), dim3(64), lds_res, stream, (const TT *)sample, \
-                           (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, n1r,  \
-                           lp.n_wg, tw, wN, means, ssq, ws);                                                        \
-    } while (0)
-            if (dim > 16 && (uint64_t)2 * n_chains * dim >= (1ull << 31))
-                return MMCMC_ERR_SHAPE;
-            if (dtype == MMCMC_F32)
-                MM_RES_LAUNCH(float);
-            else
-                MM_RES_LAUNCH(double);
-#undef MM_RES_LAUNCH
-        } else {
-#define MM_LONG_LAUNCH(TT)                                                                                          \
-    hipLaunchKernelGGL(mm_chain_fft_long_kernel<TT>, dim3(grid), dim3(64), kStatsLongLds, stream, (const TT *)sample, \
-                       (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, lp.n_wg, tw, wN, \
-                       means, ssq, ws)
-            if (dtype == MMCMC_F32)
-                MM_LONG_LAUNCH(float);
-            else
-                MM_LONG_LAUNCH(double);
-#undef MM_LONG_LAUNCH
-        }
-        MM_HIP(hipGetLastError());
-        const unsigned int total_b = (unsigned int)(dim * lp.N);
-        const unsigned int nb_red = (total_b + 63) / 64 * n_parts, nb_wb = wb_part ? (unsigned int)dim * MM_WB_CHUNKS : 0u;
-        hipLaunchKernelGGL(mm_stats_tail_kernel, dim3(nb_red + nb_wb), dim3(256), 0, stream, ws, lp.n_wg, (unsigned int)dim, lp.N,
-                           bins, nb_red, n_parts, means, ssq, (unsigned long long)(2 * n_chains), (float)m, wb_part);
-        MM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(mm_fft_psum_kernel, dim3((total_b + 255) / 256), dim3(256), 0, stream, bins, n_parts, (size_t)total_b, P);
-        hipLaunchKernelGGL(mm_fft_finish_long_kernel, dim3((unsigned int)dim * (unsigned int)((m + 31) / 32)), dim3(256), 0, stream, P,
-                           (unsigned int)dim, lp.N, (unsigned int)m, reinterpret_cast<const double *>(wN + lp.N),
-                           final_out ? final_out : acov_sum);
-        MM_HIP(hipGetLastError());
-        if (!slabs_ws)
-            MM_HIP(hipFreeAsync(ws, stream));
-        if (parts_out)
-            *parts_out = final_out ? 0 : 1;
-        return MMCMC_OK;
-    }
-    unsigned int n_slabs = stats_n_slabs(n_chains);
-    /* the per-wave lag sums: the caller's workspace (synchronous path) or a stream-ordered allocation */
-    float *slabs = slabs_ws;
-    /* lag sums on the matrix cores (one 16 x 16 tile per 256 lags) unless the half-chain is too long for LDS */
-    const unsigned int n_tiles = (unsigned int)((m + 255) / 256);
-    const size_t row_len = 240 + 256 * (size_t)(n_tiles - 1) + m + 36, row_pitch = row_len + row_len / 16 + 1;
-    const size_t lds_mfma = ((size_t)dim * row_pitch + (size_t)dim * m) * sizeof(float);
-    const int sel = g_stats_kernel.load(std::memory_order_relaxed); /* mmcmc_stats_set_kernel */
-    const bool force_direct = sel == MMCMC_STATS_KERNEL_DIRECT, force_mfma = sel == MMCMC_STATS_KERNEL_MFMA,
-               force_tile = sel == MMCMC_STATS_KERNEL_TILE;
-    /* register tiles on the vector ALU where a lane's share of the D x tiles(m) tiles fits its registers (at most 8
-     * tiles of 16 lag sums: [., 400, 3] just fits) */
-    const size_t tiles_total = dim * (size_t)stats_tile_count(m);
-    const unsigned int tpl = (unsigned int)((tiles_total + 63) / 64);
-    const size_t pitch_t = 12 * ((m + 8 + 16 + 8 + 7) / 8) + 4; /* the kernel's row pitch */
-    const size_t lds_tile = (dim * pitch_t + dim * m + 64 * 16) * sizeof(float);
-    /* one parameter per wave, a parameter's tiles dealt to `parts` waves of three slots (mm_half_chain_tile1_kernel: four
-     * waves per SIMD): half-chains up to 512 long -- eight column loads per lane, 16 waves' rows in a CU's LDS --;
-     * MMCMC_STATS_KERNEL=tile keeps the all-parameters kernel where that one applies */
-    const unsigned int tiles_1 = stats_tile_count(m);
-    const unsigned int tpl_1 = tiles_1 <= 64 ? 1u : tiles_1 <= 128 ? 2u : 3u;
-    const unsigned int parts = (tiles_1 + 64u * tpl_1 - 1u) / (64u * tpl_1);
-    const size_t lds_1 = (pitch_t + m + 64 * 16 + 64) * sizeof(float);
-    const bool no_force = !force_direct && !force_mfma;
-    const bool per_param = no_force && m <= 512 && 16 * lds_1 <= 160 * 1024 && (size_t)parts * dim <= n_slabs && !force_tile;
-    if (per_param || (tpl <= 8 && lds_tile <= 40 * 1024 && /* 8 tiles = 128 lag sums + operands = 218 registers: two waves per SIMD */ no_force)) {
-        if (!slabs)
-            MM_HIP(hipMallocAsync((void **)&slabs, (size_t)n_slabs * dim * m * sizeof(float), stream));
-        if (per_param) {
-            /* slabs x parts x parameters waves = the resident 16 per CU; the tail sums slabs x parts rows per (d, lag) */
-            const size_t cap = mm_tuning_env("MMCMC_STATS_WAVES") ? (size_t)n_slabs : 4096 / dim;
-            n_slabs = (unsigned int)std::max<size_t>(1, std::min<size_t>(n_slabs, cap) / parts);
-#define MM_TILE1_LAUNCH(TT, TPLV, NPREV)                                                                            \
-    hipLaunchKernelGGL((mm_half_chain_tile1_kernel<TT, TPLV, NPREV>), dim3(n_slabs * parts * (unsigned int)dim), dim3(64), lds_1, \
-                       stream, (const TT *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, \
-                       (unsigned int)m, parts, means, ssq, slabs)
-#define MM_TILE1_PICK(TT)                                                                                           \
-    do {                                                                                                            \
-        if (m > 256)                                                                                                \
-            MM_TILE1_LAUNCH(TT, 3, 8);                                                                              \
-        else if (tpl_1 == 1)                                                                                        \
-            MM_TILE1_LAUNCH(TT, 1, 4);                                                                              \
-        else if (tpl_1 == 2)                                                                                        \
-            MM_TILE1_LAUNCH(TT, 2, 4);                                                                              \
-        else                                                                                                        \
-            MM_TILE1_LAUNCH(TT, 3, 4);                                                                              \
-    } while (0)
-            if (dtype == MMCMC_F32)
-                MM_TILE1_PICK(float);
-            else
-                MM_TILE1_PICK(double);
-            n_slabs *= parts; /* rows the tail kernel sums */
-#undef MM_TILE1_PICK
-#undef MM_TILE1_LAUNCH
-        } else {
-        /* this kernel holds two waves per SIMD (250 registers): exactly the resident waves, each with a longer list of
-         * half-chains (measured at [65 536, 400, 3]: 1024 waves 0.62 ms, 2048 0.39, 4096 0.43, 8192 0.54) */
-        if (!mm_tuning_env("MMCMC_STATS_WAVES"))
-            n_slabs = std::min(n_slabs, 2048u);
-        /* 16-byte loads where every half-chain's [m, D] block starts on a 16-byte boundary and is whole vectors long */
-        const bool vec_ok = dtype == MMCMC_F32 && (n * dim) % 4 == 0 && ((n - m) * dim) % 4 == 0 && (m * dim) % 4 == 0 &&
-                            ((uintptr_t)sample % 16) == 0 && m * dim <= 4 * 256;
-#define MM_TILE_LAUNCH1(TT, TPLV, VECV)                                                                             \
-    hipLaunchKernelGGL((mm_half_chain_tile_kernel<TT, TPLV, VECV>), dim3(n_slabs), dim3(64), lds_tile, stream,      \
-                       (const TT *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim,        \
-                       (unsigned int)m, means, ssq, slabs)
-#define MM_TILE_LAUNCH(TT, TPLV)                                                                                    \
-    do {                                                                                                            \
-        if (sizeof(TT) == 4 && vec_ok)                                                                              \
-            MM_TILE_LAUNCH1(float, TPLV, true);                                                                     \
-        else                                                                                                        \
-            MM_TILE_LAUNCH1(TT, TPLV, false);                                                                       \
-    } while (0)
-#define MM_TILE_PICK(TT)                                                                                            \
-    do {                                                                                                            \
-        if (tpl <= 2)                                                                                               \
-            MM_TILE_LAUNCH(TT, 2);                                                                                  \
-        else if (tpl <= 4)                                                                                          \
-            MM_TILE_LAUNCH(TT, 4);                                                                                  \
-        else                                                                                                        \
-            MM_TILE_LAUNCH(TT, 8);                                                                                  \
-    } while (0)
-        if (dtype == MMCMC_F32)
-            MM_TILE_PICK(float);
-        else
-            MM_TILE_PICK(double);
-#undef MM_TILE_PICK
-#undef MM_TILE_LAUNCH
-#undef MM_TILE_LAUNCH1
-        }
-    } else if (lds_mfma <= 64 * 1024 && !force_direct) {
-        if (!slabs)
-            MM_HIP(hipMallocAsync((void **)&slabs, (size_t)n_slabs * dim * m * sizeof(float), stream));
-        if (dtype == MMCMC_F32)
-            hipLaunchKernelGGL(mm_half_chain_mfma_kernel<float>, dim3(n_slabs), dim3(64), lds_mfma, stream,
-                               (const float *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim,
-                               (unsigned int)m, n_tiles, means, ssq, slabs);
-        else
-            hipLaunchKernelGGL(mm_half_chain_mfma_kernel<double>, dim3(n_slabs), dim3(64), lds_mfma, stream,
-                               (const double *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim,
-                               (unsigned int)m, n_tiles, means, ssq, slabs);
-    } else {
-        const unsigned int m_pad = (unsigned int)(m + 64 + ((m + 64) % 2 == 0 ? 1 : 0)); /* odd row pitch */
-        const size_t lds = ((size_t)dim * m_pad + (size_t)dim * m) * sizeof(float);
-        if (lds > 160 * 1024 || m > 16384) {
-            /* nothing stages such a half-chain (or only one wave per half-chain would: [2, 32770, 1] 46 ms against 1 ms here):
-             * moments and lag sums straight from global memory, any length */
-            /* 32-bit quantities of this path: the moments kernel's grid (2 C D workgroups) and dim * m (the tail kernel's
-             * element count); and a WORK bound -- the lag sums here cost C * D * m^2 products like the reference's
-             * brute-force branch (stats.rs:622-654), ~6e12 per second on this device: past the limit (default 2^46, about ten
-             * seconds; mmcmc_stats_set_direct_work_limit moves or removes it) the call is refused instead of occupying the device
-             * for minutes.  Round 6: under AUTO / FFT this path is reached only beyond 131 072 draws per half-chain -- up to
-             * there the power spectrum is taken residue by residue (mm_chain_fft_res_kernel), e.g. [65536, 40000, 3] */
-            if ((uint64_t)dim * m >= (1ull << 32) || (uint64_t)2 * n_chains * dim >= (1ull << 31))
-                return MMCMC_ERR_SHAPE;
-            {
-                const uint64_t limit = g_stats_direct_work_limit.load(std::memory_order_relaxed); /* mmcmc_stats_set_direct_work_limit */
-                if (limit != 0 && (long double)n_chains * (long double)dim * (long double)m * (long double)m > (long double)limit)
-                    return MMCMC_ERR_UNSUPPORTED;
-            }
-            n_slabs = std::min(n_slabs, 16u);
-            if (!slabs)
-                MM_HIP(hipMallocAsync((void **)&slabs, (size_t)n_slabs * dim * m * sizeof(float), stream));
-            const unsigned int g_mom = (unsigned int)(2 * n_chains * dim);
-            const dim3 g_lag((unsigned int)((m + 255) / 256), (unsigned int)dim, n_slabs);
-            if (dtype == MMCMC_F32) {
-                hipLaunchKernelGGL(mm_half_chain_moments_any_kernel<float>, dim3(g_mom), dim3(64), 0, stream, (const float *)sample,
-                                   (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, means, ssq);
-                hipLaunchKernelGGL(mm_lag_sums_any_kernel<float>, g_lag, dim3(256), 0, stream, (const float *)sample,
-                                   (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, means, n_slabs,
-                                   slabs);
-            } else {
-                hipLaunchKernelGGL(mm_half_chain_moments_any_kernel<double>, dim3(g_mom), dim3(64), 0, stream, (const double *)sample,
-                                   (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, means, ssq);
-                hipLaunchKernelGGL(mm_lag_sums_any_kernel<double>, g_lag, dim3(256), 0, stream, (const double *)sample,
-                                   (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, means, n_slabs,
-                                   slabs);
-            }
-        } else {
-        if (!slabs)
-            MM_HIP(hipMallocAsync((void **)&slabs, (size_t)n_slabs * dim * m * sizeof(float), stream));
-        if (lds > 64 * 1024) {
-            const void *fn = dtype == MMCMC_F32 ? (const void *)mm_half_chain_kernel<float>
-                                                : (const void *)mm_half_chain_kernel<double>;
-            MM_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        if (dtype == MMCMC_F32)
-            hipLaunchKernelGGL(mm_half_chain_kernel<float>, dim3(n_slabs), dim3(64), lds, stream, (const float *)sample,
-                               (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim, (unsigned int)m, m_pad,
-                               means, ssq, slabs);
-        else
-            hipLaunchKernelGGL(mm_half_chain_kernel<double>, dim3(n_slabs), dim3(64), lds, stream,
-                               (const double *)sample, (unsigned long long)n_chains, (unsigned int)n, (unsigned int)dim,
-                               (unsigned int)m, m_pad, means, ssq, slabs);
-        }
-    }
     MM_HIP(hipGetLastError());
-    const unsigned int total = (unsigned int)(dim * m);
-    /* acov_sum: [n_parts][m, D] partial totals (n_parts = 1: the total) */
-    const unsigned int nb_red = (total + 63) / 64 * n_parts, nb_wb = wb_part ? (unsigned int)dim * MM_WB_CHUNKS : 0u;
-    hipLaunchKernelGGL(mm_stats_tail_kernel, dim3(nb_red + nb_wb), dim3(256), 0, stream, slabs, n_slabs,
-                       (unsigned int)dim, (unsigned int)m, acov_sum, nb_red, n_parts, means, ssq,
-                       (unsigned long long)(2 * n_chains), (float)m, wb_part);
+    /* rows -> n_parts partial totals: of the lag sums, the result; or of the bins, for the finish */
+    hipLaunchKernelGGL(mm_stats_tail_kernel, dim3(p.tail.gx), dim3(p.tail.block), 0, stream, c.slabs, p.rows, c.dim, p.row_len,
+                       p.writes_total ? bins : partials, p.nb_red, n_parts, means, ssq, (unsigned long long)(2 * n_chains), (float)m,
+                       wb_part);
     MM_HIP(hipGetLastError());
+    if (p.finish_kind == MM_STATS_FINISH_FFT) {
+        hipLaunchKernelGGL(mm_fft_finish_kernel, dim3(p.finish.gx), dim3(p.finish.block), p.finish.lds, stream, bins, n_parts, c.dim,
+                           p.row_len, m, stats_fft_cos_table(tw, p.r1), total);
+        MM_HIP(hipGetLastError());
+    } else if (p.finish_kind == MM_STATS_FINISH_LONG) {
+        double *P = reinterpret_cast<double *>(ws + p.off_P);
+        hipLaunchKernelGGL(mm_fft_psum_kernel, dim3(p.sum.gx), dim3(p.sum.block), 0, stream, bins, n_parts, p.len_P / 2, P);
+        hipLaunchKernelGGL(mm_fft_finish_long_kernel, dim3(p.finish.gx), dim3(p.finish.block), 0, stream, P, c.dim, p.row_len, m,
+                           reinterpret_cast<const double *>(wN + p.row_len), total);
+        MM_HIP(hipGetLastError());
+    }
     if (!slabs_ws)
-        MM_HIP(hipFreeAsync(slabs, stream));
+        MM_HIP(hipFreeAsync(ws, stream));
+    *wrote_total = p.writes_total;
     return MMCMC_OK;
 }
 
@@ -2309,16 +2042,17 @@ int mmcmc_stats_partials(const void *sample, int dtype, size_t n_chains, size_t 
         void *stream = nullptr;
     };
     static thread_local Ws w;
+    /* fewer than two draws: MMCMC_ERR_INVALID_ARG here, MMCMC_ERR_SHAPE from mmcmc_split_rhat_mean_ess; both answers are kept */
     if (!sample || n_chains == 0 || dim == 0 || n / 2 < 1)
         return MMCMC_ERR_INVALID_ARG;
-    if (n >= (1ull << 31) || dim >= (1u << 16) || !stats_bins_fit(n, dim))
-        return MMCMC_ERR_SHAPE;
-    int st = mm_check_device(device);
+    int st = mm_stats_shape_status(n, dim);
+    if (st == MMCMC_OK)
+        st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
     DevGuard g(device);
     const size_t m = n / 2, total = m * dim;
-    const size_t need = stats_ws_floats(n_chains, n, dim, kParts, device) + (size_t)kParts * total;
+    const size_t need = mm_stats_ws_floats(n_chains, n, dim, kParts, stats_knobs()) + (size_t)kParts * total;
     if (w.p && (w.device != device || w.stream != stream_v || need > w.cap)) {
         DevGuard gw(w.device);
         (void)hipDeviceSynchronize();
@@ -2335,15 +2069,13 @@ int mmcmc_stats_partials(const void *sample, int dtype, size_t n_chains, size_t 
     w.device = device;
     w.stream = stream_v;
     float *parts = w.p, *slabs = w.p + (size_t)kParts * total;
-    unsigned int n_written = kParts;
-    st = stats_partials_impl(sample, dtype, n_chains, n, dim, means, ssq, parts, nullptr, slabs, kParts, device, stream_v,
-                             &n_written, acov_sum);
-    if (st != MMCMC_OK)
+    bool wrote_total = false;
+    st = stats_partials_impl(sample, dtype, n_chains, n, dim, means, ssq, parts, acov_sum, nullptr, slabs, kParts, device, stream_v,
+                             &wrote_total);
+    if (st != MMCMC_OK || wrote_total) /* the power-spectrum paths write acov_sum themselves */
         return st;
-    if (n_written == 0) /* the power-spectrum path wrote acov_sum itself */
-        return MMCMC_OK;
     hipLaunchKernelGGL(mm_parts_sum_kernel, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream_v, parts, n_written, (unsigned int)total, acov_sum);
+                       (hipStream_t)stream_v, parts, kParts, (unsigned int)total, acov_sum);
     MM_HIP(hipGetLastError());
     return MMCMC_OK;
 }
@@ -2424,9 +2156,9 @@ int mmcmc_split_rhat_mean_ess(const void *sample, int sample_is_device, int dtyp
     if (!sample || !rhat || !ess || n_chains == 0 || dim == 0)
         return MMCMC_ERR_INVALID_ARG;
     const size_t m = n / 2;
-    if (m < 1 || n >= (1ull << 31) || dim >= (1u << 16) || !stats_bins_fit(n, dim))
-        return MMCMC_ERR_SHAPE;
-    int st = mm_check_device(device);
+    int st = mm_stats_shape_status(n, dim);
+    if (st == MMCMC_OK)
+        st = mm_check_device(device);
     if (st != MMCMC_OK)
         return st;
     DevGuard g(device);
@@ -2459,7 +2191,7 @@ int mmcmc_split_rhat_mean_ess(const void *sample, int sample_is_device, int dtyp
                 hipSuccess)
                 break;
         }
-        const size_t n_slab_floats = stats_ws_floats(n_chains, n, dim, kParts, device);
+        const size_t n_slab_floats = mm_stats_ws_floats(n_chains, n, dim, kParts, stats_knobs());
         if (!(d_buf = stats_workspace(device, nb + n_slab_floats))) {
             e = hipErrorOutOfMemory;
             break;
@@ -2471,13 +2203,14 @@ int mmcmc_split_rhat_mean_ess(const void *sample, int sample_is_device, int dtyp
          * kernels cost more than the reduction's tail (round 5: 0.150 -> see DESIGN.md 5.2) */
         float *d_acov = h;
         double *d_wb = reinterpret_cast<double *>(h + n_acov);
-        unsigned int n_written = kParts;
-        rc = stats_partials_impl(sample_is_device ? sample : d_sample, dtype, n_chains, n, dim, d_means, d_ssq, d_acov,
-                                 d_wb, d_buf + nb, kParts, device, stream_v, &n_written);
+        bool wrote_total = false; /* the total, or kParts partial totals, in the same place */
+        rc = stats_partials_impl(sample_is_device ? sample : d_sample, dtype, n_chains, n, dim, d_means, d_ssq, d_acov, d_acov,
+                                 d_wb, d_buf + nb, kParts, device, stream_v, &wrote_total);
         if (rc != MMCMC_OK)
             break;
         if ((e = stats_wait(device, stream)) != hipSuccess)
             break;
+        const unsigned int n_written = wrote_total ? 1u : kParts;
         for (size_t i = 0; i < m * dim; ++i) { /* lag sums: the partial totals in their fixed order */
             float t = h[i];
             for (unsigned int part = 1; part < n_written; ++part)

@@ -36,7 +36,7 @@ def kernels(so):
             if m:
                 name = m.group(1)
                 out[name] = ([], figures.get(name, {}))
-            elif name and ln.startswith("\t"):
+            elif name and ln.startswith("\t") and ln.strip() != "...":  # "...": zero fill up to the next symbol, no instruction
                 out[name][0].append(ln.split("//")[0].strip())
     return out
 
