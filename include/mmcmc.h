@@ -45,7 +45,9 @@ extern "C" {
  *   mmcmc_nuts_group_adapt_state, mmcmc_nuts_group_set_adapt_state, mmcmc_nuts_group_set_target_accept_p;
  *   rank-normalised diagnostics: mmcmc_rank_normalize, mmcmc_quantiles, mmcmc_rank_diagnostics;
  *   mmcmc_group_bind_collectives; the diagonal metric: mmcmc_{hmc,nuts}_set_metric, mmcmc_{hmc,nuts}_metric; the dense
- *   metric: mmcmc_{hmc,nuts}_set_metric_dense, mmcmc_{hmc,nuts}_metric_dense.
+ *   metric: mmcmc_{hmc,nuts}_set_metric_dense, mmcmc_{hmc,nuts}_metric_dense; NUTS's per-draw statistics:
+ *   mmcmc_nuts_set_draw_stats, mmcmc_nuts_draw_stats_enabled, mmcmc_nuts_draw_stats, mmcmc_nuts_draw_summary,
+ *   mmcmc_nuts_group_set_draw_stats.
  * A binding checks mmcmc_version() >= the version it was generated from (rust/mini-mcmc-hip: assert_abi, in every constructor). */
 #define MMCMC_VERSION 102 /* 0.1.2 */
 
@@ -333,6 +335,53 @@ int mmcmc_nuts_sync(mmcmc_nuts *h);
 int mmcmc_nuts_timing(mmcmc_nuts *h, mmcmc_timing *t);
 int mmcmc_nuts_destroy(mmcmc_nuts *h);
 
+/* Per-draw sampler statistics (not in the reference).  Additive: MMCMC_VERSION stays 102.
+ * One 16-byte record per chain and per ROW of the sample that mmcmc_nuts_run / mmcmc_nuts_run_progress returns, laid out
+ * [n_chains, n_rows] and indexed exactly like the sample's first two axes. */
+typedef struct mmcmc_nuts_draw {
+    float accept_stat; /* alpha / n_alpha exactly as dual averaging is fed it (the last doubling only, the kept quirk), computed in the
+                          scalar type, converted once */
+    float step_size;   /* the epsilon this transition's tree was built with, scalar type -> float */
+    float energy;      /* the Hamiltonian level of the trajectory: -(logp(x) - 1/2 p0.p0) at the transition's start, x the position
+                          before it and p0 the momentum drawn for it -- the level the tree holds, exact; NOT evaluated at the
+                          selected point.  Scalar type -> float */
+    uint32_t tree;     /* bits 0..15 leapfrog steps of this transition (<= 4095), 16..19 tree depth, 24 divergent, 25 depth cap,
+                          31 no transition */
+} mmcmc_nuts_draw;
+/*   divergent (bit 24): some leaf of the transition left the slice by more than 1000, (ln u - 1000) < joint' failed (a NaN
+ *     joint' fails it); such a leaf ends the tree, so there is at most one.  depth cap (bit 25): depth >= max_depth.
+ *   no transition (bit 31): the row is not the result of a transition -- row 0 of a progress = 0 run with n_discard == 0, the
+ *     initial position.  Its floats are NaN except step_size, which holds the current epsilon; its other bits are 0.
+ * mmcmc_nuts_set_draw_stats(h, on): recording from the next run on; off frees the buffer.  The handle owns a device buffer of
+ *   n_chains * n_rows * 16 bytes that grows on demand: 420 MB at 65 536 chains x 400 rows, more than that run's 3-D f32
+ *   sample.  Recording changes no result and touches nothing else: seed, chain offset, iteration counter, adaptation records,
+ *   leapfrog counts, depth histogram and checkpoints are what they are without it.
+ *   While recording is on the handle runs the stats unit of its target, compiled on the first enable of a (target kind,
+ *   dimension, compiler, metric kind) and verified bit for bit before use: mmcmc_nuts_kernel_variant reports 7,
+ *   set_kernel_variant to anything else returns MMCMC_ERR_UNSUPPORTED, and the variant the handle had comes back when
+ *   recording is switched off.  A metric may be set or cleared while recording is on and the other way round; each setter
+ *   leaves the other's state intact.  MMCMC_ERR_UNSUPPORTED, and nothing changed: a dimension above 32, no run-time compiler,
+ *   a unit that does not build or fails its verification.  Device groups do not record (mmcmc_nuts_group_set_draw_stats).
+ * mmcmc_nuts_draw_stats_enabled: 1 / 0, or a negative status.
+ * mmcmc_nuts_draw_stats: the records of the last run made with recording on, [n_chains, *n_rows], to host or device memory
+ *   (16-byte aligned); out may be NULL to ask for n_rows alone.  MMCMC_ERR_SHAPE if there was no such run.  Waits for the run.
+ * mmcmc_nuts_draw_summary: per chain, over the records that have a transition, on `device` (one wave per chain, float64
+ *   sums): rec [n_chains, n_rows] in host or device memory, out host [n_chains].  ebfmi = sum_{t >= 2} (E_t - E_{t-1})^2 /
+ *   sum_t (E_t - mean E)^2 over consecutive transition records, NaN with fewer than two transitions or a zero denominator;
+ *   the two means are NaN without a transition.  MMCMC_ERR_INVALID_ARG: NULL out, NULL rec with n_rows > 0, zero chains, a
+ *   device pointer that is not 16-byte aligned, a device index out of range; MMCMC_ERR_NO_DEVICE without a device;
+ *   MMCMC_ERR_SHAPE: n_rows >= 2^32 or a byte count beyond size_t. */
+typedef struct mmcmc_nuts_chain_summary {
+    uint32_t n_transitions, n_divergent, n_depth_cap, max_depth_seen;
+    uint64_t n_leapfrog;
+    double mean_accept, mean_step, ebfmi;
+} mmcmc_nuts_chain_summary;
+int mmcmc_nuts_set_draw_stats(mmcmc_nuts *h, int on);
+int mmcmc_nuts_draw_stats_enabled(mmcmc_nuts *h);
+int mmcmc_nuts_draw_stats(mmcmc_nuts *h, mmcmc_nuts_draw *out, int out_is_device, size_t *n_rows);
+int mmcmc_nuts_draw_summary(const mmcmc_nuts_draw *rec, int rec_is_device, size_t n_chains, size_t n_rows, int device,
+                            mmcmc_nuts_chain_summary *out);
+
 /* knobs shared by the samplers:
  * iterations per kernel launch (0 = the whole run in one launch, the default) -- never changes a result;
  * kernel variant: 2 = noise of two iterations packed and software-pipelined (default up to dim 16 in f64, at dim 16 in
@@ -549,6 +598,7 @@ int mmcmc_nuts_group_set_chain_offset(mmcmc_nuts_group *g, uint64_t first_global
 int mmcmc_nuts_group_set_max_depth(mmcmc_nuts_group *g, int max_depth);
 int mmcmc_nuts_group_run(mmcmc_nuts_group *g, size_t n_collect, size_t n_discard, void *out_host, int progress);
 int mmcmc_nuts_group_stats_phases(mmcmc_nuts_group *g, double *ms3);
+int mmcmc_nuts_group_set_draw_stats(mmcmc_nuts_group *g, int on); /* MMCMC_ERR_UNSUPPORTED: a device group records no per-draw statistics */
 int mmcmc_nuts_group_state(mmcmc_nuts_group *g, void *out); /* host [n_chains, dim] of the tensor type */
 int mmcmc_nuts_group_leapfrog_counts(mmcmc_nuts_group *g, uint64_t *out); /* host [n_chains] */
 int mmcmc_nuts_group_split_rhat_mean_ess(mmcmc_nuts_group *g, float *rhat, float *ess, int *used_rccl);

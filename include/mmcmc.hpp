@@ -781,6 +781,33 @@ template <class T> class NUTS {
         check(mmcmc_nuts_set_iteration(h_, iteration), "mmcmc_nuts_set_iteration");
         return *this;
     }
+    /* per-draw statistics (mmcmc_nuts_set_draw_stats): one mmcmc_nuts_draw per chain and sample row from the next run on; no
+     * result changes.  draw_stats(): the records of the last run, [n_chains, n_rows] with n_rows in *n_rows_out;
+     * draw_summary(): their per-chain summary (mmcmc_nuts_draw_summary) */
+    NUTS &set_draw_stats(bool on = true)
+    {
+        check(mmcmc_nuts_set_draw_stats(h_, on ? 1 : 0), "mmcmc_nuts_set_draw_stats");
+        return *this;
+    }
+    bool draw_stats_enabled() { return mmcmc_nuts_draw_stats_enabled(h_) == 1; }
+    std::vector<mmcmc_nuts_draw> draw_stats(size_t *n_rows_out = nullptr)
+    {
+        size_t n_rows = 0;
+        check(mmcmc_nuts_draw_stats(h_, nullptr, 0, &n_rows), "mmcmc_nuts_draw_stats");
+        std::vector<mmcmc_nuts_draw> out(n_chains_ * n_rows);
+        check(mmcmc_nuts_draw_stats(h_, out.data(), 0, nullptr), "mmcmc_nuts_draw_stats");
+        if (n_rows_out)
+            *n_rows_out = n_rows;
+        return out;
+    }
+    std::vector<mmcmc_nuts_chain_summary> draw_summary(int device = 0)
+    {
+        size_t n_rows = 0;
+        const std::vector<mmcmc_nuts_draw> rec = draw_stats(&n_rows);
+        std::vector<mmcmc_nuts_chain_summary> out(n_chains_);
+        check(mmcmc_nuts_draw_summary(rec.data(), 0, n_chains_, n_rows, device, out.data()), "mmcmc_nuts_draw_summary");
+        return out;
+    }
     /* NUTS::run -> [n_chains, n_collect, dim] (f32, the backend's element type) */
     std::vector<float> run(size_t n_collect, size_t n_discard)
     {
@@ -981,6 +1008,33 @@ class NUTS64 {
     {
         check(mmcmc_nuts_set_iteration(h_, iteration), "mmcmc_nuts_set_iteration");
         return *this;
+    }
+    /* per-draw statistics (mmcmc_nuts_set_draw_stats): one mmcmc_nuts_draw per chain and sample row from the next run on; no
+     * result changes.  draw_stats(): the records of the last run, [n_chains, n_rows] with n_rows in *n_rows_out;
+     * draw_summary(): their per-chain summary (mmcmc_nuts_draw_summary) */
+    NUTS64 &set_draw_stats(bool on = true)
+    {
+        check(mmcmc_nuts_set_draw_stats(h_, on ? 1 : 0), "mmcmc_nuts_set_draw_stats");
+        return *this;
+    }
+    bool draw_stats_enabled() { return mmcmc_nuts_draw_stats_enabled(h_) == 1; }
+    std::vector<mmcmc_nuts_draw> draw_stats(size_t *n_rows_out = nullptr)
+    {
+        size_t n_rows = 0;
+        check(mmcmc_nuts_draw_stats(h_, nullptr, 0, &n_rows), "mmcmc_nuts_draw_stats");
+        std::vector<mmcmc_nuts_draw> out(n_chains_ * n_rows);
+        check(mmcmc_nuts_draw_stats(h_, out.data(), 0, nullptr), "mmcmc_nuts_draw_stats");
+        if (n_rows_out)
+            *n_rows_out = n_rows;
+        return out;
+    }
+    std::vector<mmcmc_nuts_chain_summary> draw_summary(int device = 0)
+    {
+        size_t n_rows = 0;
+        const std::vector<mmcmc_nuts_draw> rec = draw_stats(&n_rows);
+        std::vector<mmcmc_nuts_chain_summary> out(n_chains_);
+        check(mmcmc_nuts_draw_summary(rec.data(), 0, n_chains_, n_rows, device, out.data()), "mmcmc_nuts_draw_summary");
+        return out;
     }
     NUTS64 &set_max_depth(int d)
     {

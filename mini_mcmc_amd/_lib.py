@@ -50,6 +50,17 @@ class Timing(C.Structure):
     ]
 
 
+class NutsDraw(C.Structure):
+    """mmcmc_nuts_draw: one 16-byte record per chain and sample row"""
+    _fields_ = [("accept_stat", C.c_float), ("step_size", C.c_float), ("energy", C.c_float), ("tree", C.c_uint32)]
+
+
+class NutsChainSummary(C.Structure):
+    """mmcmc_nuts_chain_summary"""
+    _fields_ = [("n_transitions", C.c_uint32), ("n_divergent", C.c_uint32), ("n_depth_cap", C.c_uint32), ("max_depth_seen", C.c_uint32),
+                ("n_leapfrog", C.c_uint64), ("mean_accept", C.c_double), ("mean_step", C.c_double), ("ebfmi", C.c_double)]
+
+
 class MmcmcError(RuntimeError):
     def __init__(self, status: int, where: str):
         self.status = status
@@ -265,6 +276,12 @@ SIGNATURES = {
     "mmcmc_hmc_metric_dense": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "mmcmc_nuts_set_metric_dense": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "mmcmc_nuts_metric_dense": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    # per-draw sampler statistics of NUTS (include/mmcmc.h: "Per-draw sampler statistics"; csrc/mm_draw_stats.hip)
+    "mmcmc_nuts_set_draw_stats": (C.c_int, [_vp, C.c_int]),
+    "mmcmc_nuts_draw_stats_enabled": (C.c_int, [_vp]),
+    "mmcmc_nuts_draw_stats": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_size_t)]),
+    "mmcmc_nuts_draw_summary": (C.c_int, [_vp, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(NutsChainSummary)]),
+    "mmcmc_nuts_group_set_draw_stats": (C.c_int, [_vp, C.c_int]),
     # rank-normalised diagnostics (csrc/mm_rank.hip)
     "mmcmc_rank_normalize": (C.c_int, [_vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _vp, C.c_int, _vp,
                                        C.c_int, _vp]),

@@ -1044,6 +1044,8 @@ int mmcmc_nuts_group_run(mmcmc_nuts_group *h, size_t n_collect, size_t n_discard
     h->g->progress = progress ? 1 : 0;
     return group_run(h->g, n_collect, n_discard, out_host, nullptr, false);
 }
+/* per-draw statistics (mmcmc_nuts_set_draw_stats) are a single handle's: a device group does not record, and nothing changes */
+int mmcmc_nuts_group_set_draw_stats(mmcmc_nuts_group *h, int) { return h ? MMCMC_ERR_UNSUPPORTED : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_nuts_group_stats_phases(mmcmc_nuts_group *h, double *ms3) { return h ? group_stats_phases(h->g, ms3) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_nuts_group_state(mmcmc_nuts_group *h, void *out) { return h ? group_state(h->g, out) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_nuts_group_leapfrog_counts(mmcmc_nuts_group *h, uint64_t *out)

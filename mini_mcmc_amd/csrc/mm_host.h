@@ -52,4 +52,9 @@ struct DevGuard {
 
 } // namespace
 
+/* mm_nuts_api.hip, for mm_progress.hip: which rows of the last run's per-draw records (mmcmc_nuts_draw_stats) belong to the sample
+ * the caller holds -- mmcmc_nuts_run_progress records every state and returns the last n_collect.  Not exported. */
+struct mmcmc_nuts;
+__attribute__((visibility("hidden"))) int mm_nuts_draw_stats_window(mmcmc_nuts *h, size_t first_row, size_t n_rows);
+
 #endif /* MM_HOST_H */

@@ -140,7 +140,7 @@ private:
     }
 };
 
-/* What the two metric_unit_verified functions (mm_api.hip, mm_nuts_api.hip) run a unit on, in float64; each converts to its
+/* What metric_unit_verified (mm_api.hip) and unit_verified (mm_nuts_api.hip) run a unit on, in float64; each converts to its
  * element type, the scale and the factor through mm_diag_prepare / mm_dense_prepare.  The start of n chains [n, D], a general
  * scale [D], and a general factor [D, D] with that diagonal and large off-diagonal entries. */
 static inline std::vector<double> mm_probe_start(size_t n, size_t D)

@@ -231,6 +231,42 @@ struct mm_nuts_info {
     uint32_t n_leapfrog; /* gradient evaluations inside the tree */
 };
 
+/* What a transition reports of itself per draw (include/mmcmc.h: mmcmc_nuts_draw, the same 16 bytes): not in the reference.
+ * accept_stat = alpha / n_alpha exactly as finish() feeds it to dual averaging (the last doubling only, the kept quirk),
+ * step_size = the epsilon the tree was built with, energy = -joint of begin_with(), each computed in ST and converted once;
+ * tree = n_leapfrog | depth << 16 | divergent << 24 | depth cap << 25 | no transition << 31. */
+struct alignas(16) mm_nuts_draw {
+    float accept_stat, step_size, energy;
+    uint32_t tree;
+};
+#define MM_DRAW_DIVERGENT (1u << 24)
+#define MM_DRAW_DEPTH_CAP (1u << 25)
+#define MM_DRAW_NONE (1u << 31)
+/* the record of a sample row that no transition produced (row 0 of a run without burn-in: the initial position) */
+template <class ST> MM_HD mm_nuts_draw mm_nuts_draw_none(ST epsilon)
+{
+    mm_nuts_draw d;
+    d.accept_stat = MM_NAN_F;
+    d.step_size = (float)epsilon;
+    d.energy = MM_NAN_F;
+    d.tree = MM_DRAW_NONE;
+    return d;
+}
+/* Rec, the recording policy of mm_nuts_tree, is a base like Met.  The default is empty and its hooks compile to nothing;
+ * mm_draw_recorder keeps one flag: some leaf of the transition failed (logu - 1000) < jointp (a NaN jointp fails it).  Such
+ * a leaf ends the tree, so there is at most one. */
+struct mm_no_recorder {
+    static constexpr bool records = false;
+    MM_HD void rec_begin() {}
+    MM_HD void rec_leaf(bool) {}
+};
+struct mm_draw_recorder {
+    static constexpr bool records = true;
+    bool diverged;
+    MM_HD void rec_begin() { diverged = false; }
+    MM_HD void rec_leaf(bool inside) { diverged = diverged || !inside; }
+};
+
 /* One transition (nuts.rs:550-691) as a resumable object: begin() | { double_begin() | leaf_step() until it
  * returns true | double_end() } while `s` | finish().  mm_nuts_step below runs these back to back (the host build, the
  * lane-synchronous kernel); the lane-asynchronous kernel (mm_nuts_kernels.h) calls them under masks, one leaf per
@@ -238,8 +274,9 @@ struct mm_nuts_info {
  * chain goes through exactly the same operations in the same order.
  * The outer edge in direction v is advanced on a copy (cx, cp, cg) and written back when the doubling ends. */
 /* Met (mm_samplers.h) is a base: the empty mm_no_metric adds nothing to the object; a mm_diag_metric is set once per chain
- * (set_metric) and read by the leapfrog and by the stop criterion */
-template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric> struct mm_nuts_tree : Met {
+ * (set_metric) and read by the leapfrog and by the stop criterion.  Rec (above) is a second base: empty by default too */
+template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric, class Rec = mm_no_recorder>
+struct mm_nuts_tree : Met, Rec {
     static constexpr int D = Tgt::dim;
     MM_HD const Met &metric() const { return *this; }
     MM_HD void set_metric(const Met &met) { static_cast<Met &>(*this) = met; }
@@ -326,6 +363,7 @@ template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, c
         n_alpha = 0;
         info.depth = 0;
         info.n_leapfrog = 0;
+        this->rec_begin();
     }
 
     template <bool PRE = false> MM_HD void double_begin(const mm_nuts_adapt<ST> &ad, uint64_t seed, uint64_t chain)
@@ -361,6 +399,7 @@ template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, c
         S_level = 0;
         S_n = (logu < jointp) ? 1u : 0u;
         S_s = (logu - ST(1000)) < jointp;
+        this->rec_leaf(S_s);
         S_alpha = mm_accept_stat<ST>(jointp - joint);
         S_nalpha = 1;
         MM_UNROLL
@@ -563,6 +602,19 @@ template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, c
         info.depth = j;
     }
 
+    /* the draw's record, assembled where finish() is called and before it: `epsilon` = ad.epsilon, the step the tree was
+     * built with (finish() replaces it).  Rec = mm_draw_recorder only. */
+    MM_HD mm_nuts_draw draw(ST epsilon, int max_depth) const
+    {
+        mm_nuts_draw d;
+        d.accept_stat = (float)(alpha / (ST)n_alpha);
+        d.step_size = (float)epsilon;
+        d.energy = (float)(-joint);
+        d.tree = (info.n_leapfrog & 0xffffu) | (((uint32_t)info.depth & 15u) << 16) | (this->diverged ? MM_DRAW_DIVERGENT : 0u) |
+                 (info.depth >= max_depth ? MM_DRAW_DEPTH_CAP : 0u);
+        return d;
+    }
+
     /* dual averaging (nuts.rs:676-690) */
     MM_HD void finish(mm_nuts_adapt<ST> *ad, uint32_t n_discard, ST target_accept_p) const
     {
@@ -580,12 +632,13 @@ template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, c
 };
 
 /* nuts.rs:550-691.  x[D] is updated in place; m is the 1-based global step count (self.m after the increment). */
-template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric>
+/* Rec = mm_draw_recorder: *rec receives the draw's record; with the empty policy it is not touched */
+template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric, class Rec = mm_no_recorder>
 MM_HD mm_nuts_info mm_nuts_step(const mm_tparams<TT> &P, TT *x, mm_nuts_adapt<ST> *ad, uint32_t m, uint32_t n_discard,
                                 ST target_accept_p, int max_depth, uint64_t seed, uint64_t chain,
-                                const mm_nuts_stack<TT, ST, Tgt::dim> &stk, const Met &met = Met())
+                                const mm_nuts_stack<TT, ST, Tgt::dim> &stk, const Met &met = Met(), mm_nuts_draw *rec = nullptr)
 {
-    mm_nuts_tree<TT, ST, Tgt, Red, Met> t;
+    mm_nuts_tree<TT, ST, Tgt, Red, Met, Rec> t;
     t.set_metric(met);
     t.begin(P, x, m, seed, chain);
     while (t.s) {
@@ -594,6 +647,8 @@ MM_HD mm_nuts_info mm_nuts_step(const mm_tparams<TT> &P, TT *x, mm_nuts_adapt<ST
         }
         t.double_end(x, seed, chain, max_depth);
     }
+    if constexpr (Rec::records)
+        *rec = t.draw(ad->epsilon, max_depth);
     t.finish(ad, n_discard, target_accept_p);
     return t.info;
 }
@@ -601,12 +656,12 @@ MM_HD mm_nuts_info mm_nuts_step(const mm_tparams<TT> &P, TT *x, mm_nuts_adapt<ST
 /* The same transition with the leaves taken in pairs (pair_first / pair_second / hand_up_free): the order in which
  * mm_nuts_pair_kernel walks a tree, run here back to back.  Bit-identical to mm_nuts_step by construction; the host
  * build compares the two (tests/test_nuts_parity_cpu.py). */
-template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric>
+template <class TT, class ST, class Tgt, class Red = mm_red_seq<TT, Tgt::dim>, class Met = mm_no_metric, class Rec = mm_no_recorder>
 MM_HD mm_nuts_info mm_nuts_step_pairs(const mm_tparams<TT> &P, TT *x, mm_nuts_adapt<ST> *ad, uint32_t m, uint32_t n_discard,
                                       ST target_accept_p, int max_depth, uint64_t seed, uint64_t chain,
-                                      const mm_nuts_stack<TT, ST, Tgt::dim> &stk, const Met &met = Met())
+                                      const mm_nuts_stack<TT, ST, Tgt::dim> &stk, const Met &met = Met(), mm_nuts_draw *rec = nullptr)
 {
-    using Tree = mm_nuts_tree<TT, ST, Tgt, Red, Met>;
+    using Tree = mm_nuts_tree<TT, ST, Tgt, Red, Met, Rec>;
     Tree t;
     t.set_metric(met);
     t.begin(P, x, m, seed, chain);
@@ -627,6 +682,8 @@ MM_HD mm_nuts_info mm_nuts_step_pairs(const mm_tparams<TT> &P, TT *x, mm_nuts_ad
         }
         t.double_end(x, seed, chain, max_depth);
     }
+    if constexpr (Rec::records)
+        *rec = t.draw(ad->epsilon, max_depth);
     t.finish(ad, n_discard, target_accept_p);
     return t.info;
 }

@@ -44,7 +44,14 @@ struct NutsBase {
     virtual int depth_histogram(uint32_t *out) = 0;
     virtual int set_variant(int v) = 0;
     virtual int set_metric(bool dense, const double *values) = 0;
+    virtual int set_draw_stats(bool on) = 0;
+    virtual int draw_stats(mmcmc_nuts_draw *out, int out_is_device, size_t *n_rows) = 0;
+    virtual int draw_stats_window(size_t first, size_t rows) = 0;
     mm_metric_record met; /* the metric that is set (mmcmc_nuts_set_metric, _set_metric_dense; mm_metric_host.h) */
+    /* per-draw statistics (mmcmc_nuts_set_draw_stats): while on the handle runs a stats unit, variant 7, like a handle with a
+     * metric.  The variant to return to is kept once: by `met` while a metric is set, else here. */
+    bool recording = false;
+    int variant_before_recording = 0;
     int variant = 0; /* 0: one chain per lane, lanes in step; 4: one chain per lane, asynchronous lanes (default for
                       * dim <= 8); 1: lane-group / MFMA (mm_nuts_lg.h); 2: + tree-depth compaction, one
                         launch per level; 3: + compaction by a persistent scheduler */
@@ -88,6 +95,13 @@ template <class TT, class ST> struct Nuts : NutsBase {
     const mm_user_target *metric_unit = nullptr, *dense_unit = nullptr;
     TT *d_metric = nullptr;
     unsigned char *d_metric_scratch = nullptr;
+    /* while recording: the stats unit per metric kind (mm_rtc_stats_unit; its kernels' stack is d_metric_scratch too), and the
+     * records of the last run, d_rec [n_chains, rec_stride] of which rows rec_first .. rec_first + rec_rows are the rows of the
+     * sample the caller got (run_progress records every row and returns the last n_collect) */
+    const mm_user_target *stats_unit[3] = {nullptr, nullptr, nullptr};
+    mm_nuts_draw *d_rec = nullptr;
+    size_t rec_capacity = 0, rec_stride = 0, rec_first = 0, rec_rows = 0;
+    bool rec_valid = false;
     TT *d_gstore = nullptr;
     int gstore_depth = 0;
     size_t g_pad = 0;
@@ -125,6 +139,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
         (void)hipFree(d_gstore);
         (void)hipFree(d_metric);
         (void)hipFree(d_metric_scratch);
+        (void)hipFree(d_rec);
         (void)hipFree(d_lg_scratch);
         (void)hipFree(d_lg_rec);
         (void)hipFree(d_lg_lists);
@@ -163,38 +178,42 @@ template <class TT, class ST> struct Nuts : NutsBase {
 
     static constexpr int type_mode_of = std::is_same<TT, double>::value ? 2 : (std::is_same<ST, double>::value ? 0 : 1);
 
-    /* the kernels of the handle's metric unit (the dense one while a dense metric is set, `dense`): init_chain, and a run by
-     * the pair kernel (which = 2: what handles launch) or with the lanes in step (which = 0: the second opinion of
-     * metric_unit_verified); `scratch` = the stack area, one unit_sizes() block per wave.  met = s, r (diagonal) or L, L^-1
-     * packed by rows (dense): the kind decides which argument block is filled, the launch is the same */
-    template <class Diag, class Dense, class A>
-    hipError_t metric_launch(const mm_user_target *unit, bool dense, const A &a, int which, const TT *met, size_t lds, hipStream_t st)
+    /* One launch of a kernel of a metric unit or of a stats unit: init_chain (which = 1), a run by the pair kernel (which = 2:
+     * what handles launch) or with the lanes in step (which = 0: the second opinion of unit_verified).  The argument block is `a`
+     * followed by what the unit adds, each pointer where the kernels' structs have it (mm_nuts_kernels.h: mm_nuts_*metric_args,
+     * mm_nuts_*dense_args, mm_nuts_stats_args; `a` ends on a pointer boundary): the metric's image met = s, r (diagonal) or L,
+     * L^-1 packed by rows (dense), then, for the run kernels of a stats unit (`stats`), the records */
+    template <class A>
+    hipError_t unit_launch(const mm_user_target *unit, int metric_kind, const A &a, int which, const TT *met, bool stats, mm_nuts_draw *rec,
+                           size_t lds, hipStream_t st)
     {
-        Diag md;
-        Dense mL;
-        void *m = &md;
-        size_t m_bytes = sizeof(md);
-        if (!dense) {
-            md.a = a;
-            md.metric = met;
-        } else {
-            mL.a = a;
-            mL.chol = met;
-            mL.chol_inv = met + mm_tri_len((size_t)dim);
-            m = &mL, m_bytes = sizeof(mL);
-        }
-        return mm_rtc_launch_nuts(unit, type_mode_of, which, m, m_bytes, (unsigned int)((a.n_chains + 63) / 64), lds, st);
+        static_assert(sizeof(A) % sizeof(void *) == 0 && alignof(A) == alignof(void *), "the pointers follow the block without padding");
+        alignas(8) unsigned char block[sizeof(A) + 3 * sizeof(void *)];
+        size_t n = sizeof(A);
+        std::memcpy(block, &a, n);
+        auto push = [&](const void *p) {
+            std::memcpy(block + n, &p, sizeof p);
+            n += sizeof p;
+        };
+        if (metric_kind != MM_METRIC_NONE)
+            push(met);
+        if (metric_kind == MM_METRIC_DENSE)
+            push(met + mm_tri_len((size_t)dim));
+        if (stats)
+            push(rec);
+        return mm_rtc_launch_nuts(unit, type_mode_of, which, block, n, (unsigned int)((a.n_chains + 63) / 64), lds, st);
     }
-    hipError_t metric_init(const mm_user_target *unit, const mm_nuts_init_args<TT, ST> &ia, const TT *met, hipStream_t st, bool dense)
+    hipError_t unit_init(const mm_user_target *unit, int metric_kind, const mm_nuts_init_args<TT, ST> &ia, const TT *met, hipStream_t st)
     {
-        return metric_launch<mm_nuts_init_metric_args<TT, ST>, mm_nuts_init_dense_args<TT, ST>>(unit, dense, ia, 1, met, 0, st);
+        return unit_launch(unit, metric_kind, ia, 1, met, false, nullptr, 0, st);
     }
-    hipError_t metric_run(const mm_user_target *unit, const mm_nuts_args<TT, ST> &a, int which, const TT *met, hipStream_t st, bool dense)
+    /* `scratch` of a = the stack area, one unit_sizes() block per wave */
+    hipError_t unit_run(const mm_user_target *unit, int metric_kind, const mm_nuts_args<TT, ST> &a, int which, const TT *met, bool stats,
+                        mm_nuts_draw *rec, hipStream_t st)
     {
         size_t stack = 0, tile = 0;
         unit_sizes((size_t)dim, &stack, &tile);
-        return metric_launch<mm_nuts_metric_args<TT, ST>, mm_nuts_dense_args<TT, ST>>(unit, dense, a, which, met,
-                                                                                     which == 2 ? (size_t)MM_NUTS_RING * 64 * sizeof(double) : tile, st);
+        return unit_launch(unit, metric_kind, a, which, met, stats, rec, which == 2 ? (size_t)MM_NUTS_RING * 64 * sizeof(double) : tile, st);
     }
 
     /* The metric unit is checked once per (unit, type mode) and process before a handle relies on it, like the units of
@@ -202,9 +221,12 @@ template <class TT, class ST> struct Nuts : NutsBase {
      * 5 + 5 transitions from a fixed start under a general metric, (a) twice by the pair kernel -- the same bits --, (b) by
      * the unit's lanes-in-step kernel, which must agree bit for bit, under rtc_unit_verified's condition on the compiler
      * that built the unit.  Only real verdicts are cached.
-     * dense: a dense-metric unit, checked the same way under a general factor with large off-diagonal entries. */
-    bool metric_unit_verified(const mm_user_target *unit, bool dense)
+     * metric_kind MM_METRIC_DENSE: a dense-metric unit, checked the same way under a general factor with large off-diagonal
+     * entries.  stats: a stats unit (mm_rtc_stats_unit) of that metric kind, MM_METRIC_NONE included: the same runs with their
+     * records, and samples AND records must agree bit for bit. */
+    bool unit_verified(const mm_user_target *unit, int metric_kind, bool stats)
     {
+        const bool dense = metric_kind == MM_METRIC_DENSE;
         static std::mutex mu;
         static std::map<const void *, bool> verdict;
         {
@@ -219,8 +241,8 @@ template <class TT, class ST> struct Nuts : NutsBase {
         /* the probe inputs of mm_metric_host.h, as the image a setter would upload */
         const std::vector<double> start = mm_probe_start(n, D);
         const std::vector<TT> x0(start.begin(), start.end());
-        std::vector<TT> met;
-        if (!metric_image(dense, (dense ? mm_probe_chol(D) : mm_probe_scale(D)).data(), met))
+        std::vector<TT> met(1, TT(0)); /* no metric: a block nobody reads */
+        if (metric_kind != MM_METRIC_NONE && !metric_image(dense, (dense ? mm_probe_chol(D) : mm_probe_scale(D)).data(), met))
             return false;
         std::vector<mm_nuts_adapt<ST>> ad0(n);
         for (auto &a : ad0) {
@@ -233,8 +255,10 @@ template <class TT, class ST> struct Nuts : NutsBase {
             TT *x = nullptr, *out = nullptr, *met = nullptr;
             mm_nuts_adapt<ST> *ad = nullptr;
             unsigned char *scratch = nullptr;
+            mm_nuts_draw *rec = nullptr;
             ~Dev()
             {
+                (void)hipFree(rec);
                 (void)hipFree(x);
                 (void)hipFree(out);
                 (void)hipFree(met);
@@ -244,12 +268,14 @@ template <class TT, class ST> struct Nuts : NutsBase {
         } d;
         if (hipMalloc((void **)&d.x, n * D * sizeof(TT)) != hipSuccess || hipMalloc((void **)&d.out, n * nc * D * sizeof(TT)) != hipSuccess ||
             hipMalloc((void **)&d.met, met.size() * sizeof(TT)) != hipSuccess || hipMalloc((void **)&d.ad, n * sizeof(mm_nuts_adapt<ST>)) != hipSuccess ||
-            hipMalloc((void **)&d.scratch, waves * stack) != hipSuccess ||
+            hipMalloc((void **)&d.scratch, waves * stack) != hipSuccess || (stats && hipMalloc((void **)&d.rec, n * nc * sizeof(mm_nuts_draw)) != hipSuccess) ||
             hipMemcpy(d.met, met.data(), met.size() * sizeof(TT), hipMemcpyHostToDevice) != hipSuccess)
             return false;
-        auto one = [&](int which, std::vector<TT> &got) -> bool {
+        auto one = [&](int which, std::vector<TT> &got, std::vector<unsigned char> &got_rec) -> bool {
             got.assign(n * nc * D, TT(0));
-            if (hipMemcpy(d.x, x0.data(), n * D * sizeof(TT), hipMemcpyHostToDevice) != hipSuccess ||
+            got_rec.assign(stats ? n * nc * sizeof(mm_nuts_draw) : 0, 0);
+            if ((stats && hipMemset(d.rec, 0, got_rec.size()) != hipSuccess) ||
+                hipMemcpy(d.x, x0.data(), n * D * sizeof(TT), hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(d.ad, ad0.data(), n * sizeof(mm_nuts_adapt<ST>), hipMemcpyHostToDevice) != hipSuccess)
                 return false;
             mm_nuts_init_args<TT, ST> ia;
@@ -282,21 +308,23 @@ template <class TT, class ST> struct Nuts : NutsBase {
             a.stack_in_lds = 0;
             a.async_batch = 0;
             a.scratch = d.scratch;
-            return metric_init(unit, ia, d.met, stream, dense) == hipSuccess && metric_run(unit, a, which, d.met, stream, dense) == hipSuccess &&
+            return unit_init(unit, metric_kind, ia, d.met, stream) == hipSuccess && unit_run(unit, metric_kind, a, which, d.met, stats, d.rec, stream) == hipSuccess &&
                    hipStreamSynchronize(stream) == hipSuccess &&
-                   hipMemcpy(got.data(), d.out, got.size() * sizeof(TT), hipMemcpyDeviceToHost) == hipSuccess;
+                   hipMemcpy(got.data(), d.out, got.size() * sizeof(TT), hipMemcpyDeviceToHost) == hipSuccess &&
+                   (!stats || hipMemcpy(got_rec.data(), d.rec, got_rec.size(), hipMemcpyDeviceToHost) == hipSuccess);
         };
         std::vector<TT> a, a2, g;
-        if (!one(2, a) || !one(2, a2))
+        std::vector<unsigned char> r, r2, rg;
+        if (!one(2, a, r) || !one(2, a2, r2))
             return false;
-        bool ok = std::memcmp(a.data(), a2.data(), a.size() * sizeof(TT)) == 0;
+        bool ok = std::memcmp(a.data(), a2.data(), a.size() * sizeof(TT)) == 0 && r == r2;
         int process_hip = 0, built_hip = 0;
         (void)mmcmc_rtc_compiler_info(nullptr, 0, &process_hip, &built_hip);
         const bool referee_trusted = mm_rtc_compiler(unit) == MMCMC_RTC_COMPILER_HIPCC || (process_hip > 0 && process_hip / 100000 >= built_hip / 100000);
         if (ok && referee_trusted) {
-            if (!one(0, g))
+            if (!one(0, g, rg))
                 return false;
-            ok = std::memcmp(a.data(), g.data(), a.size() * sizeof(TT)) == 0;
+            ok = std::memcmp(a.data(), g.data(), a.size() * sizeof(TT)) == 0 && r == rg;
         }
         std::lock_guard<std::mutex> l(mu);
         verdict[unit] = ok;
@@ -322,7 +350,18 @@ template <class TT, class ST> struct Nuts : NutsBase {
     int set_metric(bool dense, const double *values) override
     {
         if (!values) {
+            if (met.kind == MM_METRIC_NONE)
+                return MMCMC_OK;
+            if (recording) { /* the handle goes on recording on the stats unit without a metric, still variant 7 */
+                DevGuard g(device);
+                if (!ready_stats_unit(MM_METRIC_NONE))
+                    return MMCMC_ERR_UNSUPPORTED;
+            }
             met.clear(variant);
+            if (recording) {
+                variant_before_recording = variant;
+                variant = mm_metric_variant;
+            }
             return MMCMC_OK;
         }
         if (dense && dim < 1)
@@ -339,21 +378,100 @@ template <class TT, class ST> struct Nuts : NutsBase {
         if (!unit)
             return MMCMC_ERR_UNSUPPORTED; /* no run-time compiler (or the unit does not build): nothing changed */
         MM_HIP(hipDeviceSynchronize()); /* behind every queued run: a metric applies from the next transition on */
-        if (!metric_unit_verified(unit, dense))
+        if (!unit_verified(unit, dense ? MM_METRIC_DENSE : MM_METRIC_DIAG, false))
+            return MMCMC_ERR_UNSUPPORTED;
+        if (recording && !ready_stats_unit(dense ? MM_METRIC_DENSE : MM_METRIC_DIAG)) /* the records go on under the new metric */
             return MMCMC_ERR_UNSUPPORTED;
         if (!d_metric) /* room for either kind: a dense metric's two packed factors */
             MM_HIP(hipMalloc((void **)&d_metric, 2 * mm_tri_len(D) * sizeof(TT)));
-        if (!d_metric_scratch) {
-            size_t stack = 0, tile = 0;
-            unit_sizes(D, &stack, &tile);
-            MM_HIP(hipMalloc((void **)&d_metric_scratch, (n_chains + 63) / 64 * stack));
-        }
+        MM_HIP(unit_scratch());
         MM_HIP(hipMemcpy(d_metric, image.data(), image.size() * sizeof(TT), hipMemcpyHostToDevice));
         kept = unit;
+        const bool first_metric = met.kind == MM_METRIC_NONE;
         if (dense)
             met.commit_dense(values, D, variant);
         else
             met.commit_diag(values, D, variant);
+        if (recording && first_metric) /* the variant to return to is the one from before recording, kept by `met` from here on */
+            met.variant_before = variant_before_recording;
+        return MMCMC_OK;
+    }
+
+    /* the stack area of a metric unit's or a stats unit's kernels */
+    hipError_t unit_scratch()
+    {
+        if (d_metric_scratch)
+            return hipSuccess;
+        size_t stack = 0, tile = 0;
+        unit_sizes((size_t)dim, &stack, &tile);
+        return hipMalloc((void **)&d_metric_scratch, (n_chains + 63) / 64 * stack);
+    }
+
+    /* the stats unit of a metric kind, built and verified (once per unit, type mode and process), or NULL with nothing changed:
+     * a dimension above 32, no run-time compiler, a unit that does not build or fails unit_verified */
+    const mm_user_target *ready_stats_unit(int metric_kind)
+    {
+        if (stats_unit[metric_kind])
+            return stats_unit[metric_kind];
+        if (dim > 32)
+            return nullptr;
+        const mm_user_target *unit = mm_rtc_stats_unit(kind, dim, metric_kind);
+        if (!unit || hipDeviceSynchronize() != hipSuccess || !unit_verified(unit, metric_kind, true))
+            return nullptr;
+        return stats_unit[metric_kind] = unit;
+    }
+
+    /* mmcmc_nuts_set_draw_stats: every check happens before any change */
+    int set_draw_stats(bool on) override
+    {
+        if (on == recording)
+            return MMCMC_OK;
+        DevGuard g(device);
+        if (!on) {
+            MM_HIP(hipDeviceSynchronize()); /* behind the run that writes the records */
+            (void)hipFree(d_rec);
+            d_rec = nullptr;
+            rec_capacity = rec_stride = rec_first = rec_rows = 0;
+            rec_valid = false;
+            recording = false;
+            if (met.kind == MM_METRIC_NONE)
+                variant = variant_before_recording;
+            return MMCMC_OK;
+        }
+        if (!ready_stats_unit(met.kind))
+            return MMCMC_ERR_UNSUPPORTED;
+        MM_HIP(unit_scratch());
+        recording = true;
+        if (met.kind == MM_METRIC_NONE) { /* with a metric the handle is on variant 7 already and `met` keeps the one to return to */
+            variant_before_recording = variant;
+            variant = mm_metric_variant;
+        }
+        return MMCMC_OK;
+    }
+
+    int draw_stats(mmcmc_nuts_draw *out, int out_is_device, size_t *n_rows) override
+    {
+        if (!recording || !rec_valid)
+            return MMCMC_ERR_SHAPE;
+        if (n_rows)
+            *n_rows = rec_rows;
+        if (!out || rec_rows == 0)
+            return MMCMC_OK;
+        DevGuard g(device);
+        MM_HIP(hipDeviceSynchronize());
+        MM_HIP(hipMemcpy2D(out, rec_rows * sizeof(mm_nuts_draw), d_rec + rec_first, rec_stride * sizeof(mm_nuts_draw), rec_rows * sizeof(mm_nuts_draw),
+                           n_chains, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+        return MMCMC_OK;
+    }
+    /* the rows of the last run's records that the caller's sample holds (mmcmc_nuts_run_progress: the last n_collect) */
+    int draw_stats_window(size_t first, size_t rows) override
+    {
+        if (!recording || !rec_valid)
+            return MMCMC_OK;
+        if (first + rows > rec_stride)
+            return MMCMC_ERR_SHAPE;
+        rec_first = first;
+        rec_rows = rows;
         return MMCMC_OK;
     }
 
@@ -487,7 +605,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
 
     int set_variant(int v) override
     {
-        if (met.kind != MM_METRIC_NONE) /* only the metric unit has kernels that read a metric: it is variant 7 until the metric is cleared */
+        if (met.kind != MM_METRIC_NONE || recording) /* only the metric unit has kernels that read a metric, only the stats unit kernels that record: it is variant 7 until the metric is cleared and recording is off */
             return v == 7 ? MMCMC_OK : (v >= 0 && v <= 7) ? MMCMC_ERR_UNSUPPORTED : MMCMC_ERR_INVALID_ARG;
         if ((v == 0 && k) || (v >= 1 && v <= 3 && lg) || (v == 4 && k && k->run_async) || (v == 5 && k && k->run_pair) ||
             (v == 6 && generic_ok) || (v == 7 && user)) {
@@ -794,7 +912,21 @@ template <class TT, class ST> struct Nuts : NutsBase {
         const unsigned int grid64 = (unsigned int)((n_chains + 63) / 64);
         hipError_t e;
         const bool has_metric = met.kind != MM_METRIC_NONE, has_dense = met.kind == MM_METRIC_DENSE;
-        const bool rtc_target = (user && variant == 7) || has_metric; /* kernels of a run-time compiled unit */
+        const bool rtc_target = (user && variant == 7) || has_metric || recording; /* kernels of a run-time compiled unit */
+        /* the unit of a handle with a metric or one that records: the stats unit of the metric kind while recording */
+        const mm_user_target *const own_unit = recording ? stats_unit[met.kind] : has_dense ? dense_unit : metric_unit;
+        if (recording) {
+            const size_t need = n_chains * n_rows;
+            if (need > rec_capacity) {
+                MM_HIP(hipDeviceSynchronize()); /* behind a queued run that writes the buffer */
+                (void)hipFree(d_rec);
+                d_rec = nullptr;
+                rec_capacity = 0;
+                rec_valid = false;
+                MM_HIP(hipMalloc((void **)&d_rec, need * sizeof(mm_nuts_draw)));
+                rec_capacity = need;
+            }
+        }
         if (rtc_target) {
             mm_nuts_init_args<TT, ST> ia;
             ia.P = P;
@@ -804,7 +936,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
             ia.seed = seed;
             ia.chain_offset = chain_offset;
             ia.eps_tol = sizeof(ST) == 4 ? (ST)1.1920929e-7 : (ST)2.220446049250313e-16;
-            e = has_metric ? metric_init(has_dense ? dense_unit : metric_unit, ia, d_metric, st, has_dense) : mm_rtc_launch_nuts(user, type_mode, 1, &ia, sizeof(ia), grid64, 0, st);
+            e = (has_metric || recording) ? unit_init(own_unit, met.kind, ia, d_metric, st) : mm_rtc_launch_nuts(user, type_mode, 1, &ia, sizeof(ia), grid64, 0, st);
         } else {
             e = use_lg ? init_lg(st) : use_generic ? launch_generic(ga, 1, st) : k->init(P, d_state, d_adapt, n_chains, seed, chain_offset, st);
         }
@@ -856,11 +988,11 @@ template <class TT, class ST> struct Nuts : NutsBase {
         }
         MM_HIP(hipEventRecord(ev0, st));
         const unsigned int a_pre = a.n_pre, a_rec = a.n_rec;
-        if (has_metric) {
-            /* the metric unit's pair kernel, its stack in the handle's metric scratch area */
+        if (has_metric || recording) {
+            /* the metric unit's or the stats unit's pair kernel, its stack in the handle's metric scratch area */
             a.scratch = d_metric_scratch;
             a.stack_in_lds = 0;
-            e = metric_run(has_dense ? dense_unit : metric_unit, a, 2, d_metric, st, has_dense);
+            e = unit_run(own_unit, met.kind, a, 2, d_metric, recording, n_rows ? d_rec : nullptr, st);
         } else if (rtc_target) {
             /* a run-time compiled target: asynchronous lanes with the leaves in pairs (mm_nuts_pair_body; dynamic LDS = the
              * ring of uniforms, stack in the scratch area).  The unit's lanes-in-step kernel (mm_nuts_run_body) is NOT
@@ -894,6 +1026,11 @@ template <class TT, class ST> struct Nuts : NutsBase {
         if (e != hipSuccess)
             return (int)e;
         MM_HIP(hipEventRecord(ev1, st));
+        if (recording) { /* the records of this run, one per row of its sample */
+            rec_stride = rec_rows = n_rows;
+            rec_first = 0;
+            rec_valid = true;
+        }
         m += a_pre + a_rec;
         timed = true;
         /* sampling launches of this run (the persistent scheduler of a fresh handle: a 16-transition pilot plus the
@@ -1204,6 +1341,12 @@ int mmcmc_nuts_metric(mmcmc_nuts *h, double *scale_out)
 }
 int mmcmc_nuts_set_metric_dense(mmcmc_nuts *h, const double *chol) { return h ? h->p->set_metric(true, chol) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_nuts_metric_dense(mmcmc_nuts *h, double *chol_out) { return h && chol_out ? h->p->met.report_chol(chol_out) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_nuts_set_draw_stats(mmcmc_nuts *h, int on) { return h ? h->p->set_draw_stats(on != 0) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_nuts_draw_stats_enabled(mmcmc_nuts *h) { return h ? (h->p->recording ? 1 : 0) : MMCMC_ERR_INVALID_ARG; }
+int mmcmc_nuts_draw_stats(mmcmc_nuts *h, mmcmc_nuts_draw *out, int out_is_device, size_t *n_rows)
+{
+    return h ? h->p->draw_stats(out, out_is_device, n_rows) : MMCMC_ERR_INVALID_ARG;
+}
 int mmcmc_nuts_set_state(mmcmc_nuts *h, const void *x, int is_device, void *stream)
 {
     return (h && x) ? h->p->set_state(x, is_device, stream) : MMCMC_ERR_INVALID_ARG;
@@ -1290,3 +1433,5 @@ int mmcmc_nuts_destroy(mmcmc_nuts *h)
 }
 
 } /* extern "C" */
+
+int mm_nuts_draw_stats_window(mmcmc_nuts *h, size_t first_row, size_t n_rows) { return h ? h->p->draw_stats_window(first_row, n_rows) : MMCMC_ERR_INVALID_ARG; }

@@ -104,8 +104,10 @@ __global__ void mm_nuts_init_kernel(const mm_tparams<TT> P, const TT *state, mm_
 
 /* LDS_STACK is a template parameter, not a run-time choice: a pointer that may be LDS or HBM is a generic pointer and
  * every stack access a flat_load / flat_store (which is what these kernels did at first, stack "in LDS" included). */
-template <class TT, class ST, class Tgt, bool LDS_STACK, class Met = mm_no_metric>
-__device__ __forceinline__ void mm_nuts_run_body(const mm_nuts_args<TT, ST> &a, const Met &met = Met())
+/* Rec = mm_draw_recorder (mm_nuts.h; the stats units of mm_rtc.hip only): every sample row's record goes to
+ * rec[c * n_total + row], the row the sample row goes to, as one 16-byte store by the owning lane */
+template <class TT, class ST, class Tgt, bool LDS_STACK, class Met = mm_no_metric, class Rec = mm_no_recorder>
+__device__ __forceinline__ void mm_nuts_run_body(const mm_nuts_args<TT, ST> &a, const Met &met = Met(), mm_nuts_draw *rec = nullptr)
 {
     constexpr int D = Tgt::dim;
     using Tile = mm_tile<TT, D>;
@@ -163,16 +165,27 @@ __device__ __forceinline__ void mm_nuts_run_body(const mm_nuts_args<TT, ST> &a, 
 
     if (a.write_initial)
         record(a.n_rec == 0);
+    [[maybe_unused]] mm_nuts_draw *const recs = rec ? rec + (c * a.n_total + a.out_t0) : nullptr; /* this chain's first record */
+    [[maybe_unused]] const unsigned int first = a.write_initial ? 1u : 0u;
+    if constexpr (Rec::records) {
+        if (a.write_initial && recs && active)
+            recs[0] = mm_nuts_draw_none(ad.epsilon);
+    }
     const unsigned int total = a.n_pre + a.n_rec;
     for (unsigned int t = 0; t < total; ++t) {
         ++m;
         /* inactive lanes take no transition: an arbitrary state could grow an arbitrarily deep tree */
         if (active) {
-            const mm_nuts_info inf = mm_nuts_step<TT, ST, Tgt>(a.P, x, &ad, m, a.n_discard, a.target_accept_p,
-                                                               a.max_depth, a.seed, chain, stk, met);
+            [[maybe_unused]] mm_nuts_draw d;
+            const mm_nuts_info inf = mm_nuts_step<TT, ST, Tgt, mm_red_seq<TT, D>, Met, Rec>(a.P, x, &ad, m, a.n_discard, a.target_accept_p,
+                                                                                           a.max_depth, a.seed, chain, stk, met, &d);
             n_lf += inf.n_leapfrog;
             if (a.depth_hist)
                 atomicAdd(&hist_lds[inf.depth < MM_NUTS_JMAX ? inf.depth : MM_NUTS_JMAX], 1u);
+            if constexpr (Rec::records) {
+                if (recs && t >= a.n_pre)
+                    recs[first + (t - a.n_pre)] = d;
+            }
         }
         __builtin_amdgcn_wave_barrier();
         if (t >= a.n_pre)
@@ -360,12 +373,12 @@ __global__ __launch_bounds__(64) void mm_nuts_async_kernel(const mm_nuts_args<TT
 #endif
 /* the kernel proper is a device function so that a run-time compiled unit (csrc/mm_rtc.hip: user targets, built-in targets
  * at dimensions without a compiled instance) can wrap it in an extern "C" kernel of its own, like mm_nuts_run_body */
-template <class TT, class ST, class Tgt, bool LDS_STACK, class Met = mm_no_metric>
-__device__ __forceinline__ void mm_nuts_pair_body(const mm_nuts_args<TT, ST> &a, const Met &met = Met())
+template <class TT, class ST, class Tgt, bool LDS_STACK, class Met = mm_no_metric, class Rec = mm_no_recorder>
+__device__ __forceinline__ void mm_nuts_pair_body(const mm_nuts_args<TT, ST> &a, const Met &met = Met(), mm_nuts_draw *rec = nullptr)
 {
     constexpr int D = Tgt::dim;
     using Lay = mm_nuts_stack_layout<TT, ST, D>;
-    using Tree = mm_nuts_tree<TT, ST, Tgt, mm_red_seq<TT, D>, Met>;
+    using Tree = mm_nuts_tree<TT, ST, Tgt, mm_red_seq<TT, D>, Met, Rec>;
     extern __shared__ __attribute__((aligned(16))) unsigned char mm_lds_raw[];
     const int lane = threadIdx.x & 63;
     __shared__ unsigned int hist_lds[MM_NUTS_JMAX + 1]; /* see mm_nuts_run_kernel */
@@ -401,6 +414,11 @@ __device__ __forceinline__ void mm_nuts_pair_body(const mm_nuts_args<TT, ST> &a,
             rows[k] = x[k];
     }
     const unsigned int first = a.write_initial ? 1u : 0u;
+    [[maybe_unused]] mm_nuts_draw *const recs = rec ? rec + (c * a.n_total + a.out_t0) : nullptr; /* this chain's first record */
+    if constexpr (Rec::records) {
+        if (a.write_initial && recs && active)
+            recs[0] = mm_nuts_draw_none(ad.epsilon);
+    }
 
     Tree T;
     T.set_metric(met);
@@ -424,6 +442,10 @@ __device__ __forceinline__ void mm_nuts_pair_body(const mm_nuts_args<TT, ST> &a,
             MM_NP_LANES(4, turn);   /* lanes served by them */
             if (turn) {
                 if (closing) {
+                    if constexpr (Rec::records) {
+                        if (done >= a.n_pre && recs)
+                            recs[first + (done - a.n_pre)] = T.draw(ad.epsilon, a.max_depth);
+                    }
                     T.finish(&ad, a.n_discard, a.target_accept_p);
                     n_lf += T.info.n_leapfrog;
                     if (a.depth_hist)
@@ -619,6 +641,39 @@ template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts
 template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_pair_dense_body(const mm_nuts_dense_args<TT, ST> &m)
 {
     mm_nuts_pair_body<TT, ST, Tgt, false>(m.a, mm_nuts_dense_of<TT, Tgt::dim>(m.chol, m.chol_inv));
+}
+
+/* The kernels of a handle that records per-draw statistics (mm_nuts.h: mm_draw_recorder), in a stats unit only
+ * (mm_rtc_stats_unit): the argument block of the handle's run kernels -- mm_nuts_args, or with a metric mm_nuts_metric_args /
+ * mm_nuts_dense_args -- followed by one pointer, rec [n_chains, n_total] records indexed like the sample's first two axes (or
+ * NULL: nothing is recorded).  init_chain records nothing: a stats unit's init kernels take the existing init blocks. */
+template <class A> struct mm_nuts_stats_args {
+    A a;
+    mm_nuts_draw *rec;
+};
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_run_stats_body(const mm_nuts_stats_args<mm_nuts_args<TT, ST>> &s)
+{
+    mm_nuts_run_body<TT, ST, Tgt, false, mm_no_metric, mm_draw_recorder>(s.a, mm_no_metric(), s.rec);
+}
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_pair_stats_body(const mm_nuts_stats_args<mm_nuts_args<TT, ST>> &s)
+{
+    mm_nuts_pair_body<TT, ST, Tgt, false, mm_no_metric, mm_draw_recorder>(s.a, mm_no_metric(), s.rec);
+}
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_run_stats_body(const mm_nuts_stats_args<mm_nuts_metric_args<TT, ST>> &s)
+{
+    mm_nuts_run_body<TT, ST, Tgt, false, mm_diag_metric<TT, Tgt::dim>, mm_draw_recorder>(s.a.a, mm_nuts_metric_of<TT, Tgt::dim>(s.a.metric), s.rec);
+}
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_pair_stats_body(const mm_nuts_stats_args<mm_nuts_metric_args<TT, ST>> &s)
+{
+    mm_nuts_pair_body<TT, ST, Tgt, false, mm_diag_metric<TT, Tgt::dim>, mm_draw_recorder>(s.a.a, mm_nuts_metric_of<TT, Tgt::dim>(s.a.metric), s.rec);
+}
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_run_stats_body(const mm_nuts_stats_args<mm_nuts_dense_args<TT, ST>> &s)
+{
+    mm_nuts_run_body<TT, ST, Tgt, false, mm_dense_metric<TT, Tgt::dim>, mm_draw_recorder>(s.a.a, mm_nuts_dense_of<TT, Tgt::dim>(s.a.chol, s.a.chol_inv), s.rec);
+}
+template <class TT, class ST, class Tgt> __device__ __forceinline__ void mm_nuts_pair_stats_body(const mm_nuts_stats_args<mm_nuts_dense_args<TT, ST>> &s)
+{
+    mm_nuts_pair_body<TT, ST, Tgt, false, mm_dense_metric<TT, Tgt::dim>, mm_draw_recorder>(s.a.a, mm_nuts_dense_of<TT, Tgt::dim>(s.a.chol, s.a.chol_inv), s.rec);
 }
 
 #if !defined(__HIPCC_RTC__) /* host side: not part of the run-time compiled kernels of user targets (mm_rtc.hip) */

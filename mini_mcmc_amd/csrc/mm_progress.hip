@@ -233,6 +233,7 @@ int mmcmc_nuts_run_progress(mmcmc_nuts *h, size_t n_collect, size_t n_discard, s
     DevBuf all, sample;
     MMP_HIP(hipMalloc(&all.p, n_chains * total * dim * esz));
     MMP(mmcmc_nuts_run(h, n_collect, n_discard, all.p, 1, 2, stream));
+    MMP(mm_nuts_draw_stats_window(h, n_discard, n_collect)); /* per-draw records, if recorded: of the sample's rows */
     if (every == 0)
         every = std::max<size_t>(1, (total + 9) / 10);
     for (size_t done = 0; done < total;) {

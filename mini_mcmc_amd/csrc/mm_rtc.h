@@ -34,6 +34,11 @@ const mm_user_target *mm_rtc_builtin_nuts(int kind, int dim); /* the same for NU
  * its own built on the first set_metric_dense: the same launchers, the argument blocks mm_run_dense_args<T> /
  * mm_nuts_init_dense_args / mm_nuts_dense_args (the factors' pointers at the end) */
 const mm_user_target *mm_rtc_metric_unit(int kind, int dim, bool dense);
+/* the stats unit of the same kinds at dim <= 32, built on the first mmcmc_nuts_set_draw_stats of a (kind, dimension, compiler,
+ * metric kind 0 none / 1 diagonal / 2 dense): NUTS kernels only, answering mm_rtc_launch_nuts; the run kernels (0 lanes in step, 2
+ * pairs) take the handle's argument block for that metric kind followed by the records' pointer (mm_nuts_stats_args), init (1)
+ * takes the existing init block of that metric kind.  NULL as above */
+const mm_user_target *mm_rtc_stats_unit(int kind, int dim, int metric_kind);
 hipError_t mm_rtc_launch_discrete(const mm_user_target *t, void *args, size_t args_bytes, unsigned int grid, hipStream_t stream);
 /* kernels of a registered target: sampler 0 MH / 1 HMC, dtype 0 f32 / 1 f64; `args` = the mm_run_args<T> block */
 hipError_t mm_rtc_launch_run_split(const mm_user_target *t, int sampler, void *args, size_t args_bytes, unsigned int grid, size_t lds,

@@ -258,6 +258,12 @@ class NUTSGroup(_Group):
         L.check(L.lib().mmcmc_nuts_group_set_max_depth(self._h, int(max_depth)), "mmcmc_nuts_group_set_max_depth")
         return self
 
+    def set_draw_stats(self, on: bool = True) -> "NUTSGroup":
+        """A device group records no per-draw statistics (`nuts.NUTS.set_draw_stats`): raises MmcmcError(ERR_UNSUPPORTED), and
+        nothing changes."""
+        L.check(L.lib().mmcmc_nuts_group_set_draw_stats(self._h, 1 if on else 0), "mmcmc_nuts_group_set_draw_stats")
+        return self
+
     def run(self, n_collect: int, n_discard: int = 0, to_host: bool = True, progress: bool = False):
         """NUTS::run (N - 1 transitions, row 0 may be the initial point, nuts.rs:457-471) or, progress=True, the stepping
         of run_progress (nuts.rs:491-522); sample [n_chains, n_collect, dim] of the mode's tensor type."""

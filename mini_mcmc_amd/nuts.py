@@ -10,6 +10,19 @@ from . import checkpoint as K
 from .distributions import IsotropicGaussian, Target
 
 
+# mmcmc_nuts_draw as a numpy structured dtype: [n_chains, n_rows] records indexed like the sample's first two axes
+DRAW_DTYPE = np.dtype([("accept_stat", np.float32), ("step_size", np.float32), ("energy", np.float32), ("tree", np.uint32)])
+
+
+def unpack_tree(tree):
+    """The packed `tree` field of per-draw records -> (n_leapfrog, depth, divergent, depth_cap, transition): integer arrays for
+    the first two, boolean ones for the flags; `transition` is False for a row no transition produced (row 0 of a run without
+    burn-in, the initial position)."""
+    t = np.asarray(tree, dtype=np.uint32)
+    return (t & np.uint32(0xFFFF)).astype(np.int64), ((t >> np.uint32(16)) & np.uint32(15)).astype(np.int64), \
+        ((t >> np.uint32(24)) & np.uint32(1)).astype(bool), ((t >> np.uint32(25)) & np.uint32(1)).astype(bool), (t >> np.uint32(31)) == 0
+
+
 class NUTS(K.Checkpointable):
     """NUTS::new(target, initial_positions, target_accept_p) (nuts.rs:123-129).
 
@@ -166,6 +179,33 @@ class NUTS(K.Checkpointable):
     @metric_chol.setter
     def metric_chol(self, chol) -> None:
         K.set_metric_chol(self, chol)
+
+    def set_draw_stats(self, on: bool = True) -> "NUTS":
+        """Record one `DRAW_DTYPE` entry per chain and sample row from the next run on (accept_stat, step_size, energy, and the
+        packed tree: leapfrogs, depth, divergent, depth cap; `unpack_tree`).  No result changes; the handle runs its target's stats
+        unit (compiled on the first use, seconds; kernel_variant 7) until recording is switched off, which frees the records.
+        The buffer is n_chains * n_rows * 16 bytes on the device."""
+        L.check(L.lib().mmcmc_nuts_set_draw_stats(self._h, 1 if on else 0), "mmcmc_nuts_set_draw_stats")
+        return self
+
+    @property
+    def draw_stats_enabled(self) -> bool:
+        return L.lib().mmcmc_nuts_draw_stats_enabled(self._h) == 1
+
+    def draw_stats(self, to: str = "numpy"):
+        """The records of the last run: numpy [n_chains, n_rows] of `DRAW_DTYPE`, or with to="torch" a uint8 tensor
+        [n_chains, n_rows, 16] on the handle's device (the same bytes; stats.nuts_summary takes either)."""
+        n = C.c_size_t()
+        L.check(L.lib().mmcmc_nuts_draw_stats(self._h, None, 0, C.byref(n)), "mmcmc_nuts_draw_stats")
+        if to == "torch":
+            import torch
+
+            out = torch.empty((self.n_chains, n.value, 16), device=torch.device("cuda", self.device), dtype=torch.uint8)
+            L.check(L.lib().mmcmc_nuts_draw_stats(self._h, C.c_void_p(out.data_ptr()), 1, None), "mmcmc_nuts_draw_stats")
+            return out
+        out = np.empty((self.n_chains, n.value), dtype=DRAW_DTYPE)
+        L.check(L.lib().mmcmc_nuts_draw_stats(self._h, out.ctypes.data, 0, None), "mmcmc_nuts_draw_stats")
+        return out
 
     def _params(self):
         p, d = C.c_double(), C.c_int()

@@ -471,3 +471,64 @@ def _run_stats_from_c(rs) -> RunStats:
         return BasicStats(name, x.min, x.median, x.max, x.mean, x.std)
 
     return RunStats(b("ESS", rs.ess), b("Split R-hat", rs.rhat))
+
+
+@dataclass
+class NutsSummary:
+    """`nuts_summary`: per chain, over the records that have a transition -- counts, leapfrog total, the means of the acceptance
+    statistic and of the step size, E-BFMI (NaN with fewer than two transitions or constant energy) -- and the totals a user
+    looks at first: the number and share of divergent transitions, the share at the depth cap, the smallest E-BFMI and the
+    chain that has it (-1 when no chain has one)."""
+    n_transitions: np.ndarray
+    n_divergent: np.ndarray
+    n_depth_cap: np.ndarray
+    max_depth_seen: np.ndarray
+    n_leapfrog: np.ndarray
+    mean_accept: np.ndarray
+    mean_step: np.ndarray
+    ebfmi: np.ndarray
+    total_transitions: int
+    total_divergent: int
+    divergent_share: float
+    depth_cap_share: float
+    min_ebfmi: float
+    min_ebfmi_chain: int
+
+    def __str__(self):
+        return (f"{self.total_transitions} transitions of {len(self.n_transitions)} chains: {self.total_divergent} divergent "
+                f"({100.0 * self.divergent_share:.3f} %), {100.0 * self.depth_cap_share:.3f} % at the depth cap, smallest E-BFMI "
+                f"{self.min_ebfmi:.3f} (chain {self.min_ebfmi_chain})")
+
+
+def nuts_summary(records, device: int | None = None) -> NutsSummary:
+    """Per-chain summary of NUTS's per-draw records on the device (mmcmc_nuts_draw_summary: one wave per chain, float64 sums):
+    `records` as `NUTS.draw_stats` returns them -- numpy [chains, rows] of `nuts.DRAW_DTYPE`, or the uint8 torch tensor
+    [chains, rows, 16] on a device, which is read in place."""
+    from .nuts import DRAW_DTYPE
+
+    if type(records).__module__.startswith("torch"):
+        if records.dtype.itemsize != 1 or records.dim() != 3 or records.shape[2] != 16 or not records.is_contiguous() or records.device.type != "cuda":
+            raise ValueError("records: a contiguous uint8 tensor [chains, rows, 16] on a device")
+        n_chains, n_rows = int(records.shape[0]), int(records.shape[1])
+        ptr, is_device = C.c_void_p(records.data_ptr()), 1
+        device = records.device.index if device is None else device
+    else:
+        a = np.ascontiguousarray(records, dtype=DRAW_DTYPE)
+        if a.ndim != 2:
+            raise ValueError("records must be [chains, rows]")
+        n_chains, n_rows = a.shape
+        ptr, is_device = C.c_void_p(a.ctypes.data), 0
+        device = 0 if device is None else device
+    out = (L.NutsChainSummary * n_chains)()
+    L.check(L.lib().mmcmc_nuts_draw_summary(ptr, is_device, n_chains, n_rows, int(device), out), "mmcmc_nuts_draw_summary")
+    raw = np.frombuffer(out, dtype=np.dtype([("n_transitions", np.uint32), ("n_divergent", np.uint32), ("n_depth_cap", np.uint32),
+                                             ("max_depth_seen", np.uint32), ("n_leapfrog", np.uint64), ("mean_accept", np.float64),
+                                             ("mean_step", np.float64), ("ebfmi", np.float64)])).copy()
+    total = int(raw["n_transitions"].astype(np.int64).sum())
+    n_div = int(raw["n_divergent"].astype(np.int64).sum())
+    n_cap = int(raw["n_depth_cap"].astype(np.int64).sum())
+    has = ~np.isnan(raw["ebfmi"])
+    worst = int(np.flatnonzero(has)[np.argmin(raw["ebfmi"][has])]) if has.any() else -1
+    return NutsSummary(*(raw[k] for k in raw.dtype.names), total_transitions=total, total_divergent=n_div,
+                       divergent_share=n_div / total if total else float("nan"), depth_cap_share=n_cap / total if total else float("nan"),
+                       min_ebfmi=float(raw["ebfmi"][worst]) if worst >= 0 else float("nan"), min_ebfmi_chain=worst)
