@@ -22,8 +22,10 @@
  * ranks on one device, a device listed twice keeps the collective branch (tests/c/fake_collectives.c: N > 1 ranks on one GPU).
  */
 #include "../../include/mmcmc.h"
+#include "mm_group_plan.h"
 #include "mm_host.h"
 #include "mm_hostcopy.h"
+#include "mm_sampler_ops.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -232,9 +234,7 @@ class Worker {
 struct Shard {
     int device = 0;
     size_t first = 0, n = 0; /* global chains [first, first + n) */
-    mmcmc_hmc *hmc = nullptr;
-    mmcmc_mh *mh = nullptr;
-    mmcmc_nuts *nuts = nullptr;
+    void *handle = nullptr; /* the shard's sampler, of the type Group::ops drives */
     void *d_sample = nullptr; /* [n, n_collect, dim] of the last run, on the device */
     size_t sample_cap = 0;
     hipStream_t stream = nullptr;
@@ -246,16 +246,13 @@ struct Shard {
 };
 
 struct Group {
-    int sampler = 0; /* 0 MH, 1 HMC, 2 NUTS */
+    const mm_sampler_ops *ops = nullptr; /* what differs between MH, HMC and NUTS (mm_sampler_ops.h) */
     int progress = 0; /* NUTS: run (N - 1 transitions) or run_progress stepping (nuts.rs:457-471 / 491-522) */
     int dtype = MMCMC_F32, dim = 0;
     size_t n_chains = 0, cmax = 0;
     size_t last_collect = 0;
     bool use_rccl = false, comm_ready = false;
-    /* why the statistics travel as they do (reported through *used_rccl): 1 RCCL; 0 the host BY DESIGN (a device listed
-     * twice: RCCL refuses two ranks on one GPU); -1 the host as a FALLBACK: libnccl / librccl not found; -2: ncclCommInitAll
-     * failed (e.g. no peer access) -- a scaling run must not take the host path silently */
-    int exchange_status = 0;
+    int exchange_status = 0; /* why the statistics travel as they do (reported through *used_rccl): mm_group_exchange's values */
     /* an asynchronous run whose enqueue loop failed half way leaves the shards at different iterations: the group refuses
      * every later run / diagnostics call with MMCMC_ERR_GROUP_BROKEN instead of continuing on an inconsistent state */
     bool broken = false;
@@ -263,6 +260,31 @@ struct Group {
     uint64_t user_offset = 0;
     std::vector<Shard> sh;
     size_t esize() const { return dtype == MMCMC_F32 ? 4 : 8; }
+    ~Group()
+    {
+        /* runs may still be queued on the shards' streams (the asynchronous group_run): nothing they use may be freed under them */
+        for (Shard &s : sh)
+            if (s.stream && hipSetDevice(s.device) == hipSuccess)
+                (void)hipStreamSynchronize(s.stream);
+        for (Shard &s : sh) {
+            s.worker.reset();
+            (void)hipSetDevice(s.device);
+            if (s.comm && rccl().ok())
+                (void)rccl().CommDestroy(s.comm);
+            if (s.handle)
+                (void)ops->destroy(s.handle);
+            if (s.d_sample)
+                (void)hipFree(s.d_sample);
+            if (s.d_stats)
+                (void)hipFree(s.d_stats);
+            if (s.tev0)
+                (void)hipEventDestroy(s.tev0);
+            if (s.tev1)
+                (void)hipEventDestroy(s.tev1);
+            if (s.stream)
+                (void)hipStreamDestroy(s.stream);
+        }
+    }
 };
 
 template <class F> int for_each_shard(Group *g, F &&f)
@@ -281,42 +303,12 @@ template <class F> int for_each_shard(Group *g, F &&f)
     return st;
 }
 
-int group_destroy(Group *g)
-{
-    if (!g)
-        return MMCMC_ERR_INVALID_ARG;
-    /* runs may still be queued on the shards' streams (the asynchronous group_run): nothing they use may be freed under them */
-    for (Shard &s : g->sh)
-        if (s.stream && hipSetDevice(s.device) == hipSuccess)
-            (void)hipStreamSynchronize(s.stream);
-    for (Shard &s : g->sh) {
-        s.worker.reset();
-        (void)hipSetDevice(s.device);
-        if (s.comm && rccl().ok())
-            (void)rccl().CommDestroy(s.comm);
-        if (s.hmc)
-            (void)mmcmc_hmc_destroy(s.hmc);
-        if (s.mh)
-            (void)mmcmc_mh_destroy(s.mh);
-        if (s.nuts)
-            (void)mmcmc_nuts_destroy(s.nuts);
-        if (s.d_sample)
-            (void)hipFree(s.d_sample);
-        if (s.d_stats)
-            (void)hipFree(s.d_stats);
-        if (s.tev0)
-            (void)hipEventDestroy(s.tev0);
-        if (s.tev1)
-            (void)hipEventDestroy(s.tev1);
-        if (s.stream)
-            (void)hipStreamDestroy(s.stream);
-    }
-    delete g;
-    return MMCMC_OK;
-}
-
-int group_create(Group **out, int sampler, const mmcmc_target_desc *target, const mmcmc_proposal_desc *proposal, const void *init,
-                 size_t n_chains, double scale, int n_leapfrog, int dtype, const int *devices, int n_devices)
+/* H: the public handle (a Group).  make(&handle, init_slice, n, device) creates the sampler of one shard from its slice of
+ * `init` [n_chains, dim] (elements of ops->init_elem_size(dtype) bytes): what a sampler's create call takes beyond that
+ * stays with the mmcmc_*_group_create that passes it. */
+template <class H, class Make>
+int group_create(H **out, const mm_sampler_ops *ops, const mmcmc_target_desc *target, const void *init, size_t n_chains, int dtype,
+                 const int *devices, int n_devices, Make &&make)
 {
     if (!out)
         return MMCMC_ERR_INVALID_ARG;
@@ -327,58 +319,43 @@ int group_create(Group **out, int sampler, const mmcmc_target_desc *target, cons
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
         return MMCMC_ERR_NO_DEVICE;
-    bool dup = false;
-    for (int i = 0; i < n_devices; ++i) {
+    for (int i = 0; i < n_devices; ++i)
         if (devices[i] < 0 || devices[i] >= n_dev)
             return MMCMC_ERR_INVALID_ARG;
-        for (int j = 0; j < i; ++j)
-            dup = dup || devices[j] == devices[i];
-    }
-    Group *g = new (std::nothrow) Group();
+    H *g = new (std::nothrow) H();
     if (!g)
         return (int)hipErrorOutOfMemory;
-    g->sampler = sampler;
+    g->ops = ops;
     g->dtype = dtype;
     g->dim = target->dim;
     g->n_chains = n_chains;
-    g->use_rccl = (!dup || collectives_share_devices()) && rccl().ok();
-    g->exchange_status = g->use_rccl ? 1 : dup ? 0 : -1;
+    const bool dup = mm_group_has_duplicate(devices, n_devices), share = dup && collectives_share_devices();
+    /* the library is looked for only where the rule could use it (the first look binds it for the life of the process) */
+    const mm_group_exchange_plan ex = mm_group_exchange(dup, share, mm_group_exchange(dup, share, true).use_rccl && rccl().ok());
+    g->use_rccl = ex.use_rccl;
+    g->exchange_status = ex.status;
     g->sh.resize((size_t)n_devices);
-    const size_t esz = g->esize(), base = n_chains / (size_t)n_devices, rem = n_chains % (size_t)n_devices;
-    size_t first = 0;
+    g->cmax = mm_group_cmax(n_chains, (size_t)n_devices);
     for (int i = 0; i < n_devices; ++i) {
-        Shard &s = g->sh[(size_t)i];
-        s.device = devices[i];
-        s.first = first;
-        s.n = base + ((size_t)i < rem ? 1 : 0);
-        first += s.n;
-        g->cmax = s.n > g->cmax ? s.n : g->cmax;
+        const mm_group_slice part = mm_group_partition(n_chains, (size_t)n_devices, (size_t)i);
+        g->sh[(size_t)i].device = devices[i];
+        g->sh[(size_t)i].first = part.first;
+        g->sh[(size_t)i].n = part.n;
     }
     const int st = for_each_shard(g, [&](Shard &s, int) -> int {
-        /* NUTS: init is [n_chains, dim] doubles whatever the mode (Vec<Vec<T>>, nuts.rs:123-129); scale = target_accept_p,
-         * n_leapfrog = the type mode */
-        const char *p = (const char *)init + s.first * (size_t)g->dim * (sampler == 2 ? sizeof(double) : esz);
-        int rc = sampler == 2   ? mmcmc_nuts_create(&s.nuts, target, (const double *)p, s.n, scale, n_leapfrog, s.device)
-                 : sampler == 1 ? mmcmc_hmc_create(&s.hmc, target, p, s.n, scale, n_leapfrog, dtype, s.device)
-                                : mmcmc_mh_create(&s.mh, target, proposal, p, s.n, dtype, s.device);
+        int rc = make(&s.handle, (const char *)init + s.first * (size_t)g->dim * ops->init_elem_size(dtype), s.n, s.device);
         if (rc != MMCMC_OK)
             return rc;
-        rc = sampler == 2 ? mmcmc_nuts_set_chain_offset(s.nuts, s.first)
-                          : sampler ? mmcmc_hmc_set_chain_offset(s.hmc, s.first) : mmcmc_mh_set_chain_offset(s.mh, s.first);
+        rc = ops->set_chain_offset(s.handle, s.first);
         if (rc != MMCMC_OK)
             return rc;
-        /* nobody reads the per-handle launch timing of a shard: no event packets between back-to-back launches */
-        if (sampler == 1)
-            (void)mmcmc_hmc_enable_timing(s.hmc, 0);
-        else if (sampler == 0)
-            (void)mmcmc_mh_enable_timing(s.mh, 0);
         if (hipSetDevice(s.device) != hipSuccess)
             return MMCMC_ERR_NO_DEVICE;
         hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
         return e == hipSuccess ? MMCMC_OK : (int)e;
     });
     if (st != MMCMC_OK) {
-        group_destroy(g);
+        delete g;
         return st;
     }
     /* the communicators are made HERE, not inside the first diagnostics call: a timed reduction never pays
@@ -390,8 +367,10 @@ int group_create(Group **out, int sampler, const mmcmc_target_desc *target, cons
         for (size_t i = 0; i < N; ++i)
             devs[i] = g->sh[i].device;
         if (rccl().CommInitAll(comms.data(), (int)N, devs.data()) != 0) {
-            g->use_rccl = false; /* e.g. no peer access: the statistics travel through the host, and the status says so */
-            g->exchange_status = -2;
+            /* e.g. no peer access: the statistics travel through the host, and the status says so */
+            const mm_group_exchange_plan failed = mm_group_exchange_init_failed();
+            g->use_rccl = failed.use_rccl;
+            g->exchange_status = failed.status;
         } else {
             for (size_t i = 0; i < N; ++i)
                 g->sh[i].comm = comms[i];
@@ -402,31 +381,34 @@ int group_create(Group **out, int sampler, const mmcmc_target_desc *target, cons
     return MMCMC_OK;
 }
 
-int group_seed(Group *g, uint64_t seed)
+/* "the same call on every shard, one after the other, stop at the first failure": the argument checks first
+ * (MMCMC_ERR_INVALID_ARG), then -- for the calls that refuse a broken group, see the table above the entry points --
+ * MMCMC_ERR_GROUP_BROKEN, then f(Shard &) -> status */
+enum BrokenRule { kEvenIfBroken, kRefuseBroken };
+template <class F> int on_every_shard(Group *g, bool args_ok, BrokenRule rule, F &&f)
 {
-    if (!g)
+    if (!g || !args_ok)
         return MMCMC_ERR_INVALID_ARG;
+    if (rule == kRefuseBroken && g->broken)
+        return MMCMC_ERR_GROUP_BROKEN;
     for (Shard &s : g->sh) {
-        const int rc = g->sampler == 2 ? mmcmc_nuts_seed(s.nuts, seed) : g->sampler ? mmcmc_hmc_seed(s.hmc, seed) : mmcmc_mh_seed(s.mh, seed);
+        const int rc = f(s);
         if (rc != MMCMC_OK)
             return rc;
     }
     return MMCMC_OK;
 }
 
+int group_seed(Group *g, uint64_t seed)
+{
+    return on_every_shard(g, true, kEvenIfBroken, [&](Shard &s) { return g->ops->seed(s.handle, seed); });
+}
+
 int group_set_chain_offset(Group *g, uint64_t off)
 {
-    if (!g)
-        return MMCMC_ERR_INVALID_ARG;
-    g->user_offset = off;
-    for (Shard &s : g->sh) {
-        const int rc = g->sampler == 2 ? mmcmc_nuts_set_chain_offset(s.nuts, off + s.first)
-                       : g->sampler    ? mmcmc_hmc_set_chain_offset(s.hmc, off + s.first)
-                                       : mmcmc_mh_set_chain_offset(s.mh, off + s.first);
-        if (rc != MMCMC_OK)
-            return rc;
-    }
-    return MMCMC_OK;
+    if (g)
+        g->user_offset = off;
+    return on_every_shard(g, true, kEvenIfBroken, [&](Shard &s) { return g->ops->set_chain_offset(s.handle, off + s.first); });
 }
 
 static int shard_reserve_sample(Shard &s, size_t bytes)
@@ -460,7 +442,7 @@ int group_run(Group *g, size_t n_collect, size_t n_discard, void *out_host, uint
         return MMCMC_ERR_GROUP_BROKEN;
     const size_t esz = g->esize(), row = n_collect * (size_t)g->dim * esz;
     if (async) {
-        if (g->sampler == 2)
+        if (!g->ops->can_run_async)
             return MMCMC_ERR_UNSUPPORTED; /* NUTS hands adaptation state over between its launches: blocking only */
         DevGuard restore; /* the loops below set each shard's device */
         int st = MMCMC_OK;
@@ -480,14 +462,12 @@ int group_run(Group *g, size_t n_collect, size_t n_discard, void *out_host, uint
                     st = MMCMC_ERR_NO_DEVICE;
                     break;
                 }
-                void *d_out = n_collect ? s.d_sample : nullptr;
-                st = g->sampler ? mmcmc_hmc_run(s.hmc, n_collect, n_discard, d_out, 1, nullptr, s.stream)
-                                : mmcmc_mh_run(s.mh, n_collect, n_discard, d_out, 1, nullptr, s.stream);
+                st = g->ops->run(s.handle, n_collect, n_discard, n_collect ? s.d_sample : nullptr, nullptr, 0, s.stream);
                 if (st != MMCMC_OK)
                     break;
                 ++enqueued;
             }
-        if (st != MMCMC_OK && enqueued > 0) {
+        if (mm_group_breaks_async(enqueued, st)) {
             /* shards 0 .. enqueued - 1 have advanced, the rest have not: wait for what was queued and refuse further use */
             for (size_t i = 0; i < enqueued; ++i)
                 if (hipSetDevice(g->sh[i].device) == hipSuccess)
@@ -507,10 +487,7 @@ int group_run(Group *g, size_t n_collect, size_t n_discard, void *out_host, uint
         if (rc != MMCMC_OK)
             return rc;
         uint64_t *acc = accept_counts ? accept_counts + s.first : nullptr;
-        void *d_out = n_collect ? s.d_sample : nullptr;
-        rc = g->sampler == 2 ? mmcmc_nuts_run(s.nuts, n_collect, n_discard, d_out, 1, g->progress, s.stream)
-             : g->sampler    ? mmcmc_hmc_run(s.hmc, n_collect, n_discard, d_out, 1, acc, s.stream)
-                             : mmcmc_mh_run(s.mh, n_collect, n_discard, d_out, 1, acc, s.stream);
+        rc = g->ops->run(s.handle, n_collect, n_discard, n_collect ? s.d_sample : nullptr, acc, g->progress, s.stream);
         if (rc != MMCMC_OK)
             return rc;
         advanced[(size_t)i] = 1;
@@ -521,15 +498,14 @@ int group_run(Group *g, size_t n_collect, size_t n_discard, void *out_host, uint
             e = hipStreamSynchronize(s.stream);
         return e == hipSuccess ? MMCMC_OK : (int)e;
     });
+    /* when every shard ran but a copy or sync failed, last_collect keeps the length of the run before (kept as it is) */
     if (st == MMCMC_OK)
         g->last_collect = n_collect;
-    else {
-        size_t n_adv = 0;
-        for (char a : advanced)
-            n_adv += a ? 1 : 0;
-        if (n_adv > 0 && n_adv < g->sh.size())
-            g->broken = true; /* some shards have run and others not: same rule as the asynchronous path */
-    }
+    size_t n_adv = 0;
+    for (char a : advanced)
+        n_adv += a ? 1 : 0;
+    if (mm_group_breaks_blocking(n_adv, g->sh.size(), st))
+        g->broken = true; /* some shards have run and others not: same rule as the asynchronous path */
     return st;
 }
 
@@ -599,8 +575,7 @@ int group_state(Group *g, void *out)
     /* a broken group's shards stand at different iterations; their states are still what each shard holds -- readable */
     const size_t esz = g->esize();
     return for_each_shard(g, [&](Shard &s, int) -> int {
-        void *p = (char *)out + s.first * (size_t)g->dim * esz;
-        return g->sampler == 2 ? mmcmc_nuts_state(s.nuts, p) : g->sampler ? mmcmc_hmc_state(s.hmc, p) : mmcmc_mh_state(s.mh, p);
+        return g->ops->state(s.handle, (char *)out + s.first * (size_t)g->dim * esz);
     });
 }
 
@@ -614,10 +589,7 @@ int group_set_state(Group *g, const void *in)
         return MMCMC_ERR_GROUP_BROKEN;
     const size_t esz = g->esize();
     return for_each_shard(g, [&](Shard &s, int) -> int {
-        const void *p = (const char *)in + s.first * (size_t)g->dim * esz;
-        return g->sampler == 2 ? mmcmc_nuts_set_state(s.nuts, p, 0, s.stream)
-               : g->sampler    ? mmcmc_hmc_set_state(s.hmc, p, 0, s.stream)
-                               : mmcmc_mh_set_state(s.mh, p, 0, s.stream);
+        return g->ops->set_state(s.handle, (const char *)in + s.first * (size_t)g->dim * esz, s.stream);
     });
 }
 
@@ -628,10 +600,7 @@ int group_stream_position(Group *g, uint64_t *seed, uint64_t *first_global_chain
         return MMCMC_ERR_INVALID_ARG;
     if (g->broken)
         return MMCMC_ERR_GROUP_BROKEN; /* the shards stand at different iterations */
-    const Shard &s = g->sh[0];
-    const int rc = g->sampler == 2 ? mmcmc_nuts_stream_position(s.nuts, seed, nullptr, iteration)
-                   : g->sampler    ? mmcmc_hmc_stream_position(s.hmc, seed, nullptr, iteration)
-                                   : mmcmc_mh_stream_position(s.mh, seed, nullptr, iteration);
+    const int rc = g->ops->stream_position(g->sh[0].handle, seed, nullptr, iteration);
     if (rc == MMCMC_OK && first_global_chain)
         *first_global_chain = g->user_offset;
     return rc;
@@ -639,18 +608,7 @@ int group_stream_position(Group *g, uint64_t *seed, uint64_t *first_global_chain
 
 int group_set_iteration(Group *g, uint64_t iteration)
 {
-    if (!g || iteration >= (1ull << 32))
-        return MMCMC_ERR_INVALID_ARG;
-    if (g->broken)
-        return MMCMC_ERR_GROUP_BROKEN;
-    for (Shard &s : g->sh) {
-        const int rc = g->sampler == 2 ? mmcmc_nuts_set_iteration(s.nuts, iteration)
-                       : g->sampler    ? mmcmc_hmc_set_iteration(s.hmc, iteration)
-                                       : mmcmc_mh_set_iteration(s.mh, iteration);
-        if (rc != MMCMC_OK)
-            return rc;
-    }
-    return MMCMC_OK;
+    return on_every_shard(g, iteration < (1ull << 32), kRefuseBroken, [&](Shard &s) { return g->ops->set_iteration(s.handle, iteration); });
 }
 
 /* split-R-hat / ESS of the last run's sample (stats.rs:416-423) over ALL devices' chains */
@@ -806,18 +764,29 @@ int group_stats_phases(Group *g, double *ms3)
     return MMCMC_OK;
 }
 
+/* the typed calls only one sampler has (its fields, NUTS's adaptation records) take the shard's handle through these */
+mmcmc_mh *mh_of(const Shard &s) { return (mmcmc_mh *)s.handle; }
+mmcmc_hmc *hmc_of(const Shard &s) { return (mmcmc_hmc *)s.handle; }
+mmcmc_nuts *nuts_of(const Shard &s) { return (mmcmc_nuts *)s.handle; }
+
 } // namespace
 
-struct mmcmc_hmc_group {
-    Group *g;
-};
-struct mmcmc_mh_group {
-    Group *g;
-};
-struct mmcmc_nuts_group {
-    Group *g;
-};
+/* the public handles are the group */
+struct mmcmc_mh_group : Group {};
+struct mmcmc_hmc_group : Group {};
+struct mmcmc_nuts_group : Group {};
 
+/* Every entry point checks a NULL handle and its arguments first (MMCMC_ERR_INVALID_ARG).  Then:
+ *
+ *   refuse a broken group (MMCMC_ERR_GROUP_BROKEN)      | do not look at `broken`
+ *   ----------------------------------------------------+------------------------------------------------------------
+ *   run, run_async                                      | seed, set_chain_offset, set_max_depth (*)
+ *   set_state, stream_position, set_iteration           | state, adapt_state, leapfrog_counts, *_params, shard
+ *   split_rhat_mean_ess                                 | sync, stream_timer, exchange, stats_phases, destroy
+ *   set_step_size, set_n_leapfrog, set_proposal_std,    | set_draw_stats (always MMCMC_ERR_UNSUPPORTED)
+ *   set_target_accept_p, set_adapt_state                |
+ *
+ * (*) the odd one out among the setters: observed, not decided. */
 extern "C" {
 
 int mmcmc_group_bind_collectives(const char *library_path, int ranks_may_share_a_device)
@@ -825,83 +794,83 @@ int mmcmc_group_bind_collectives(const char *library_path, int ranks_may_share_a
     return bind_collectives(library_path, ranks_may_share_a_device);
 }
 
+/* what all three samplers' groups have */
+#define MM_GROUP_COMMON(P)                                                                                        \
+    int mmcmc_##P##_group_seed(mmcmc_##P##_group *h, uint64_t seed) { return group_seed(h, seed); }               \
+    int mmcmc_##P##_group_set_chain_offset(mmcmc_##P##_group *h, uint64_t off) { return group_set_chain_offset(h, off); } \
+    int mmcmc_##P##_group_stats_phases(mmcmc_##P##_group *h, double *ms3) { return group_stats_phases(h, ms3); }  \
+    int mmcmc_##P##_group_state(mmcmc_##P##_group *h, void *out) { return group_state(h, out); }                  \
+    int mmcmc_##P##_group_set_state(mmcmc_##P##_group *h, const void *in) { return group_set_state(h, in); }      \
+    int mmcmc_##P##_group_stream_position(mmcmc_##P##_group *h, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration) \
+    {                                                                                                             \
+        return group_stream_position(h, seed, first_global_chain, iteration);                                     \
+    }                                                                                                             \
+    int mmcmc_##P##_group_set_iteration(mmcmc_##P##_group *h, uint64_t iteration) { return group_set_iteration(h, iteration); } \
+    int mmcmc_##P##_group_split_rhat_mean_ess(mmcmc_##P##_group *h, float *rhat, float *ess, int *used_rccl)      \
+    {                                                                                                             \
+        return group_split_rhat_ess(h, rhat, ess, used_rccl);                                                     \
+    }                                                                                                             \
+    int mmcmc_##P##_group_sync(mmcmc_##P##_group *h) { return group_sync(h); }                                    \
+    int mmcmc_##P##_group_stream_timer(mmcmc_##P##_group *h, int stop, float *ms_per_device)                      \
+    {                                                                                                             \
+        return group_stream_timer(h, stop, ms_per_device);                                                        \
+    }                                                                                                             \
+    int mmcmc_##P##_group_exchange(mmcmc_##P##_group *h, int *status, int *n_rccl_ranks)                          \
+    {                                                                                                             \
+        return group_exchange(h, status, n_rccl_ranks);                                                           \
+    }                                                                                                             \
+    int mmcmc_##P##_group_destroy(mmcmc_##P##_group *h)                                                         \
+    {                                                                                                             \
+        delete h; /* ~Group */                                                                                    \
+        return h ? MMCMC_OK : MMCMC_ERR_INVALID_ARG;                                                              \
+    }
+MM_GROUP_COMMON(mh)
+MM_GROUP_COMMON(hmc)
+MM_GROUP_COMMON(nuts)
+#undef MM_GROUP_COMMON
+
+/* ---- HMC ---- */
 int mmcmc_hmc_group_create(mmcmc_hmc_group **out, const mmcmc_target_desc *target, const void *init, size_t n_chains,
                            double step_size, int n_leapfrog, int dtype, const int *devices, int n_devices)
 {
-    if (!out)
-        return MMCMC_ERR_INVALID_ARG;
-    *out = nullptr;
-    Group *g = nullptr;
-    const int st = group_create(&g, 1, target, nullptr, init, n_chains, step_size, n_leapfrog, dtype, devices, n_devices);
-    if (st != MMCMC_OK)
-        return st;
-    *out = new (std::nothrow) mmcmc_hmc_group{g};
-    if (!*out) {
-        group_destroy(g);
-        return (int)hipErrorOutOfMemory;
-    }
-    return MMCMC_OK;
+    return group_create(out, &mm_ops_hmc, target, init, n_chains, dtype, devices, n_devices,
+                        [&](void **handle, const void *x, size_t n, int device) -> int {
+                            mmcmc_hmc *h = nullptr;
+                            const int rc = mmcmc_hmc_create(&h, target, x, n, step_size, n_leapfrog, dtype, device);
+                            /* nobody reads the per-handle launch timing of a shard: no event packets between back-to-back launches */
+                            if (rc == MMCMC_OK)
+                                (void)mmcmc_hmc_enable_timing(h, 0);
+                            *handle = h;
+                            return rc;
+                        });
 }
-int mmcmc_hmc_group_seed(mmcmc_hmc_group *h, uint64_t seed) { return h ? group_seed(h->g, seed) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_hmc_group_set_chain_offset(mmcmc_hmc_group *h, uint64_t off) { return h ? group_set_chain_offset(h->g, off) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_hmc_group_run(mmcmc_hmc_group *h, size_t n_collect, size_t n_discard, void *out_host, uint64_t *accept_counts)
 {
-    return h ? group_run(h->g, n_collect, n_discard, out_host, accept_counts, false) : MMCMC_ERR_INVALID_ARG;
+    return group_run(h, n_collect, n_discard, out_host, accept_counts, false);
 }
 int mmcmc_hmc_group_run_async(mmcmc_hmc_group *h, size_t n_collect, size_t n_discard)
 {
-    return h ? group_run(h->g, n_collect, n_discard, nullptr, nullptr, true) : MMCMC_ERR_INVALID_ARG;
+    return group_run(h, n_collect, n_discard, nullptr, nullptr, true);
 }
-int mmcmc_hmc_group_stats_phases(mmcmc_hmc_group *h, double *ms3) { return h ? group_stats_phases(h->g, ms3) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_hmc_group_state(mmcmc_hmc_group *h, void *out) { return h ? group_state(h->g, out) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_hmc_group_set_state(mmcmc_hmc_group *h, const void *in) { return h ? group_set_state(h->g, in) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_hmc_group_set_step_size(mmcmc_hmc_group *h, double step_size)
 {
-    if (!h || !(step_size > 0.0) || !std::isfinite(step_size)) /* checked once: no shard changes unless all do */
-        return MMCMC_ERR_INVALID_ARG;
-    if (h->g->broken)
-        return MMCMC_ERR_GROUP_BROKEN;
-    for (Shard &s : h->g->sh) {
-        const int rc = mmcmc_hmc_set_step_size(s.hmc, step_size);
-        if (rc != MMCMC_OK)
-            return rc;
-    }
-    return MMCMC_OK;
+    /* checked once, here: no shard changes unless all do */
+    return on_every_shard(h, step_size > 0.0 && std::isfinite(step_size), kRefuseBroken,
+                          [&](Shard &s) { return mmcmc_hmc_set_step_size(hmc_of(s), step_size); });
 }
 int mmcmc_hmc_group_set_n_leapfrog(mmcmc_hmc_group *h, int n_leapfrog)
 {
-    if (!h || n_leapfrog < 0)
-        return MMCMC_ERR_INVALID_ARG;
-    if (h->g->broken)
-        return MMCMC_ERR_GROUP_BROKEN;
-    for (Shard &s : h->g->sh) {
-        const int rc = mmcmc_hmc_set_n_leapfrog(s.hmc, n_leapfrog);
-        if (rc != MMCMC_OK)
-            return rc;
-    }
-    return MMCMC_OK;
+    return on_every_shard(h, n_leapfrog >= 0, kRefuseBroken, [&](Shard &s) { return mmcmc_hmc_set_n_leapfrog(hmc_of(s), n_leapfrog); });
 }
 int mmcmc_hmc_group_params(mmcmc_hmc_group *h, double *step_size, int *n_leapfrog)
 {
-    return h ? mmcmc_hmc_params(h->g->sh[0].hmc, step_size, n_leapfrog) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_hmc_group_stream_position(mmcmc_hmc_group *h, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration)
-{
-    return h ? group_stream_position(h->g, seed, first_global_chain, iteration) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_hmc_group_set_iteration(mmcmc_hmc_group *h, uint64_t iteration)
-{
-    return h ? group_set_iteration(h->g, iteration) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_hmc_group_split_rhat_mean_ess(mmcmc_hmc_group *h, float *rhat, float *ess, int *used_rccl)
-{
-    return h ? group_split_rhat_ess(h->g, rhat, ess, used_rccl) : MMCMC_ERR_INVALID_ARG;
+    return h ? mmcmc_hmc_params(hmc_of(h->sh[0]), step_size, n_leapfrog) : MMCMC_ERR_INVALID_ARG;
 }
 int mmcmc_hmc_group_shard(mmcmc_hmc_group *h, int i, int *device, size_t *first_chain, size_t *n_chains, void **sample_dev)
 {
-    if (!h || i < 0 || (size_t)i >= h->g->sh.size())
+    if (!h || i < 0 || (size_t)i >= h->sh.size())
         return MMCMC_ERR_INVALID_ARG;
-    const Shard &s = h->g->sh[(size_t)i];
+    const Shard &s = h->sh[(size_t)i];
     if (device)
         *device = s.device;
     if (first_chain)
@@ -912,218 +881,104 @@ int mmcmc_hmc_group_shard(mmcmc_hmc_group *h, int i, int *device, size_t *first_
         *sample_dev = s.d_sample;
     return MMCMC_OK;
 }
-int mmcmc_hmc_group_sync(mmcmc_hmc_group *h) { return h ? group_sync(h->g) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_hmc_group_stream_timer(mmcmc_hmc_group *h, int stop, float *ms_per_device)
-{
-    return h ? group_stream_timer(h->g, stop, ms_per_device) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_hmc_group_exchange(mmcmc_hmc_group *h, int *status, int *n_rccl_ranks)
-{
-    return h ? group_exchange(h->g, status, n_rccl_ranks) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_hmc_group_destroy(mmcmc_hmc_group *h)
-{
-    if (!h)
-        return MMCMC_ERR_INVALID_ARG;
-    const int st = group_destroy(h->g);
-    delete h;
-    return st;
-}
 
+/* ---- MH ---- */
 int mmcmc_mh_group_create(mmcmc_mh_group **out, const mmcmc_target_desc *target, const mmcmc_proposal_desc *proposal,
                           const void *init, size_t n_chains, int dtype, const int *devices, int n_devices)
 {
-    if (!out || !proposal)
+    if (!out || !proposal) /* before anything else */
         return MMCMC_ERR_INVALID_ARG;
-    *out = nullptr;
-    Group *g = nullptr;
-    const int st = group_create(&g, 0, target, proposal, init, n_chains, proposal->std, 0, dtype, devices, n_devices);
-    if (st != MMCMC_OK)
-        return st;
-    *out = new (std::nothrow) mmcmc_mh_group{g};
-    if (!*out) {
-        group_destroy(g);
-        return (int)hipErrorOutOfMemory;
-    }
-    return MMCMC_OK;
+    return group_create(out, &mm_ops_mh, target, init, n_chains, dtype, devices, n_devices,
+                        [&](void **handle, const void *x, size_t n, int device) -> int {
+                            mmcmc_mh *h = nullptr;
+                            const int rc = mmcmc_mh_create(&h, target, proposal, x, n, dtype, device);
+                            if (rc == MMCMC_OK) /* as for HMC */
+                                (void)mmcmc_mh_enable_timing(h, 0);
+                            *handle = h;
+                            return rc;
+                        });
 }
-int mmcmc_mh_group_seed(mmcmc_mh_group *h, uint64_t seed) { return h ? group_seed(h->g, seed) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_mh_group_set_chain_offset(mmcmc_mh_group *h, uint64_t off) { return h ? group_set_chain_offset(h->g, off) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_mh_group_run(mmcmc_mh_group *h, size_t n_collect, size_t n_discard, void *out_host, uint64_t *accept_counts)
 {
-    return h ? group_run(h->g, n_collect, n_discard, out_host, accept_counts, false) : MMCMC_ERR_INVALID_ARG;
+    return group_run(h, n_collect, n_discard, out_host, accept_counts, false);
 }
 int mmcmc_mh_group_run_async(mmcmc_mh_group *h, size_t n_collect, size_t n_discard)
 {
-    return h ? group_run(h->g, n_collect, n_discard, nullptr, nullptr, true) : MMCMC_ERR_INVALID_ARG;
+    return group_run(h, n_collect, n_discard, nullptr, nullptr, true);
 }
-int mmcmc_mh_group_stats_phases(mmcmc_mh_group *h, double *ms3) { return h ? group_stats_phases(h->g, ms3) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_mh_group_state(mmcmc_mh_group *h, void *out) { return h ? group_state(h->g, out) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_mh_group_set_state(mmcmc_mh_group *h, const void *in) { return h ? group_set_state(h->g, in) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_mh_group_set_proposal_std(mmcmc_mh_group *h, double std)
 {
-    if (!h || !(std > 0.0) || !std::isfinite(std))
-        return MMCMC_ERR_INVALID_ARG;
-    if (h->g->broken)
-        return MMCMC_ERR_GROUP_BROKEN;
-    for (Shard &s : h->g->sh) {
-        const int rc = mmcmc_mh_set_proposal_std(s.mh, std);
-        if (rc != MMCMC_OK)
-            return rc;
-    }
-    return MMCMC_OK;
+    return on_every_shard(h, std > 0.0 && std::isfinite(std), kRefuseBroken, [&](Shard &s) { return mmcmc_mh_set_proposal_std(mh_of(s), std); });
 }
-int mmcmc_mh_group_params(mmcmc_mh_group *h, double *std) { return h ? mmcmc_mh_params(h->g->sh[0].mh, std) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_mh_group_stream_position(mmcmc_mh_group *h, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration)
-{
-    return h ? group_stream_position(h->g, seed, first_global_chain, iteration) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_mh_group_set_iteration(mmcmc_mh_group *h, uint64_t iteration)
-{
-    return h ? group_set_iteration(h->g, iteration) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_mh_group_split_rhat_mean_ess(mmcmc_mh_group *h, float *rhat, float *ess, int *used_rccl)
-{
-    return h ? group_split_rhat_ess(h->g, rhat, ess, used_rccl) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_mh_group_sync(mmcmc_mh_group *h) { return h ? group_sync(h->g) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_mh_group_stream_timer(mmcmc_mh_group *h, int stop, float *ms_per_device)
-{
-    return h ? group_stream_timer(h->g, stop, ms_per_device) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_mh_group_exchange(mmcmc_mh_group *h, int *status, int *n_rccl_ranks)
-{
-    return h ? group_exchange(h->g, status, n_rccl_ranks) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_mh_group_destroy(mmcmc_mh_group *h)
-{
-    if (!h)
-        return MMCMC_ERR_INVALID_ARG;
-    const int st = group_destroy(h->g);
-    delete h;
-    return st;
-}
+int mmcmc_mh_group_params(mmcmc_mh_group *h, double *std) { return h ? mmcmc_mh_params(mh_of(h->sh[0]), std) : MMCMC_ERR_INVALID_ARG; }
 
-/* NUTS::run / run_progress (nuts.rs:163-170, 194-338) over N devices: `init` [n_chains, dim] doubles, mode as in
- * mmcmc_nuts_create; the sample is of the mode's tensor type (f32 for modes 0 and 1, f64 for mode 2) */
+/* ---- NUTS::run / run_progress (nuts.rs:163-170, 194-338) over N devices: `init` [n_chains, dim] doubles, mode as in
+ * mmcmc_nuts_create; the sample is of the mode's tensor type (f32 for modes 0 and 1, f64 for mode 2) ---- */
 int mmcmc_nuts_group_create(mmcmc_nuts_group **out, const mmcmc_target_desc *target, const double *init, size_t n_chains,
                             double target_accept_p, int mode, const int *devices, int n_devices)
 {
     if (!out || mode < 0 || mode > 2)
         return MMCMC_ERR_INVALID_ARG;
-    *out = nullptr;
-    Group *g = nullptr;
-    const int st = group_create(&g, 2, target, nullptr, init, n_chains, target_accept_p, mode, mode == 2 ? MMCMC_F64 : MMCMC_F32, devices,
-                                n_devices);
-    if (st != MMCMC_OK)
-        return st;
-    *out = new (std::nothrow) mmcmc_nuts_group{g};
-    if (!*out) {
-        group_destroy(g);
-        return (int)hipErrorOutOfMemory;
-    }
-    return MMCMC_OK;
-}
-int mmcmc_nuts_group_seed(mmcmc_nuts_group *h, uint64_t seed) { return h ? group_seed(h->g, seed) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_nuts_group_set_chain_offset(mmcmc_nuts_group *h, uint64_t off) { return h ? group_set_chain_offset(h->g, off) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_nuts_group_set_max_depth(mmcmc_nuts_group *h, int max_depth)
-{
-    if (!h)
-        return MMCMC_ERR_INVALID_ARG;
-    for (Shard &s : h->g->sh) {
-        const int rc = mmcmc_nuts_set_max_depth(s.nuts, max_depth);
-        if (rc != MMCMC_OK)
-            return rc;
-    }
-    return MMCMC_OK;
+    return group_create(out, &mm_ops_nuts, target, init, n_chains, mode == 2 ? MMCMC_F64 : MMCMC_F32, devices, n_devices,
+                        [&](void **handle, const void *x, size_t n, int device) -> int {
+                            mmcmc_nuts *h = nullptr;
+                            const int rc = mmcmc_nuts_create(&h, target, (const double *)x, n, target_accept_p, mode, device);
+                            *handle = h;
+                            return rc;
+                        });
 }
 int mmcmc_nuts_group_run(mmcmc_nuts_group *h, size_t n_collect, size_t n_discard, void *out_host, int progress)
 {
     if (!h)
         return MMCMC_ERR_INVALID_ARG;
-    h->g->progress = progress ? 1 : 0;
-    return group_run(h->g, n_collect, n_discard, out_host, nullptr, false);
+    h->progress = progress ? 1 : 0; /* run (N - 1 transitions) or run_progress stepping (nuts.rs:457-471 / 491-522) */
+    return group_run(h, n_collect, n_discard, out_host, nullptr, false);
+}
+int mmcmc_nuts_group_set_max_depth(mmcmc_nuts_group *h, int max_depth)
+{
+    /* the range is the shard's check (mmcmc_nuts_set_max_depth); a broken group is not refused: see the table */
+    return on_every_shard(h, true, kEvenIfBroken, [&](Shard &s) { return mmcmc_nuts_set_max_depth(nuts_of(s), max_depth); });
+}
+int mmcmc_nuts_group_set_target_accept_p(mmcmc_nuts_group *h, double target_accept_p)
+{
+    return on_every_shard(h, target_accept_p > 0.0 && target_accept_p < 1.0, kRefuseBroken,
+                          [&](Shard &s) { return mmcmc_nuts_set_target_accept_p(nuts_of(s), target_accept_p); });
+}
+int mmcmc_nuts_group_params(mmcmc_nuts_group *h, double *target_accept_p, int *max_depth)
+{
+    return h ? mmcmc_nuts_params(nuts_of(h->sh[0]), target_accept_p, max_depth) : MMCMC_ERR_INVALID_ARG;
 }
 /* per-draw statistics (mmcmc_nuts_set_draw_stats) are a single handle's: a device group does not record, and nothing changes */
 int mmcmc_nuts_group_set_draw_stats(mmcmc_nuts_group *h, int) { return h ? MMCMC_ERR_UNSUPPORTED : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_nuts_group_stats_phases(mmcmc_nuts_group *h, double *ms3) { return h ? group_stats_phases(h->g, ms3) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_nuts_group_state(mmcmc_nuts_group *h, void *out) { return h ? group_state(h->g, out) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_nuts_group_leapfrog_counts(mmcmc_nuts_group *h, uint64_t *out)
 {
     if (!h || !out)
         return MMCMC_ERR_INVALID_ARG;
-    return for_each_shard(h->g, [&](Shard &s, int) -> int { return mmcmc_nuts_leapfrog_counts(s.nuts, out + s.first); });
+    return for_each_shard(h, [&](Shard &s, int) -> int { return mmcmc_nuts_leapfrog_counts(nuts_of(s), out + s.first); });
 }
-int mmcmc_nuts_group_set_state(mmcmc_nuts_group *h, const void *in) { return h ? group_set_state(h->g, in) : MMCMC_ERR_INVALID_ARG; }
 int mmcmc_nuts_group_adapt_state(mmcmc_nuts_group *h, double *out)
 {
     if (!h || !out)
         return MMCMC_ERR_INVALID_ARG;
-    return for_each_shard(h->g, [&](Shard &s, int) -> int { return mmcmc_nuts_adapt_state(s.nuts, out + 4 * s.first); });
+    return for_each_shard(h, [&](Shard &s, int) -> int { return mmcmc_nuts_adapt_state(nuts_of(s), out + 4 * s.first); });
 }
 int mmcmc_nuts_group_set_adapt_state(mmcmc_nuts_group *h, const double *in)
 {
     if (!h || !in)
         return MMCMC_ERR_INVALID_ARG;
-    if (h->g->broken)
+    if (h->broken)
         return MMCMC_ERR_GROUP_BROKEN;
     /* mmcmc_nuts_set_adapt_state's checks on every row first: no shard changes unless all do */
     int mode = 0;
-    (void)mmcmc_nuts_shape(h->g->sh[0].nuts, nullptr, nullptr, &mode, nullptr);
-    for (size_t i = 0; i < 4 * h->g->n_chains; ++i) {
+    (void)mmcmc_nuts_shape(nuts_of(h->sh[0]), nullptr, nullptr, &mode, nullptr);
+    for (size_t i = 0; i < 4 * h->n_chains; ++i) {
         const double v = in[i];
         if (!std::isfinite(v) || (mode == 1 && !std::isfinite((float)v)))
             return MMCMC_ERR_INVALID_ARG;
         if (i % 4 == 0 && !((mode == 1 ? (double)(float)v : v) > 0.0) && v != -1.0)
             return MMCMC_ERR_INVALID_ARG;
     }
-    return for_each_shard(h->g, [&](Shard &s, int) -> int { return mmcmc_nuts_set_adapt_state(s.nuts, in + 4 * s.first); });
-}
-int mmcmc_nuts_group_params(mmcmc_nuts_group *h, double *target_accept_p, int *max_depth)
-{
-    return h ? mmcmc_nuts_params(h->g->sh[0].nuts, target_accept_p, max_depth) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_nuts_group_set_target_accept_p(mmcmc_nuts_group *h, double target_accept_p)
-{
-    if (!h || !(target_accept_p > 0.0 && target_accept_p < 1.0))
-        return MMCMC_ERR_INVALID_ARG;
-    if (h->g->broken)
-        return MMCMC_ERR_GROUP_BROKEN;
-    for (Shard &s : h->g->sh) {
-        const int rc = mmcmc_nuts_set_target_accept_p(s.nuts, target_accept_p);
-        if (rc != MMCMC_OK)
-            return rc;
-    }
-    return MMCMC_OK;
-}
-int mmcmc_nuts_group_stream_position(mmcmc_nuts_group *h, uint64_t *seed, uint64_t *first_global_chain, uint64_t *iteration)
-{
-    return h ? group_stream_position(h->g, seed, first_global_chain, iteration) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_nuts_group_set_iteration(mmcmc_nuts_group *h, uint64_t iteration)
-{
-    return h ? group_set_iteration(h->g, iteration) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_nuts_group_split_rhat_mean_ess(mmcmc_nuts_group *h, float *rhat, float *ess, int *used_rccl)
-{
-    return h ? group_split_rhat_ess(h->g, rhat, ess, used_rccl) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_nuts_group_sync(mmcmc_nuts_group *h) { return h ? group_sync(h->g) : MMCMC_ERR_INVALID_ARG; }
-int mmcmc_nuts_group_stream_timer(mmcmc_nuts_group *h, int stop, float *ms_per_device)
-{
-    return h ? group_stream_timer(h->g, stop, ms_per_device) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_nuts_group_exchange(mmcmc_nuts_group *h, int *status, int *n_rccl_ranks)
-{
-    return h ? group_exchange(h->g, status, n_rccl_ranks) : MMCMC_ERR_INVALID_ARG;
-}
-int mmcmc_nuts_group_destroy(mmcmc_nuts_group *h)
-{
-    if (!h)
-        return MMCMC_ERR_INVALID_ARG;
-    const int st = group_destroy(h->g);
-    delete h;
-    return st;
+    return for_each_shard(h, [&](Shard &s, int) -> int { return mmcmc_nuts_set_adapt_state(nuts_of(s), in + 4 * s.first); });
 }
 
 } /* extern "C" */

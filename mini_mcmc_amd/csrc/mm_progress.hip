@@ -16,6 +16,7 @@
 #include "../../include/mmcmc.h"
 #include "mm_host.h"
 #include "mm_hostcopy.h"
+#include "mm_sampler_ops.h"
 
 #include <hip/hip_runtime.h>
 
@@ -81,13 +82,6 @@ struct TrackerOwner {
             return (int)_e;                                                                                         \
     } while (0)
 
-/* what differs between the fixed-length samplers */
-struct FixedOps {
-    int (*run_rows)(void *h, size_t n_rows, size_t n_discard, void *out_device, size_t n_total_rows, size_t row0, void *stream);
-    int (*state)(void *h, void *out_host);
-    bool per_chain_trackers; /* MH: ChainTrackers through the burn-in; HMC: one MultiChainTracker after it */
-};
-
 int report(mmcmc_tracker *tr, bool per_chain, mmcmc_progress_fn cb, void *user, uint64_t done, uint64_t total, void *stream)
 {
     if (!cb)
@@ -120,7 +114,7 @@ int finish(const void *d_out, void *out, int out_is_device, int dtype, size_t n_
     return MMCMC_OK;
 }
 
-int fixed_run_progress(void *h, const FixedOps &ops, size_t n_chains, int dim_i, int dtype, int device, size_t n_collect,
+int fixed_run_progress(void *h, const mm_sampler_ops &ops, size_t n_chains, int dim_i, int dtype, int device, size_t n_collect,
                        size_t n_discard, size_t every, mmcmc_progress_fn cb, void *user, void *out, int out_is_device,
                        mmcmc_run_stats *stats, mmcmc_tracker **tracker_out, void *stream)
 {
@@ -176,11 +170,6 @@ int fixed_run_progress(void *h, const FixedOps &ops, size_t n_chains, int dim_i,
     return finish(d_out, out, out_is_device, dtype, n_chains, n_collect, dim, stats, device, stream, tr, tracker_out);
 }
 
-int mh_rows(void *h, size_t a, size_t b, void *o, size_t c, size_t d, void *s) { return mmcmc_mh_run_rows((mmcmc_mh *)h, a, b, o, c, d, s); }
-int mh_state(void *h, void *o) { return mmcmc_mh_state((mmcmc_mh *)h, o); }
-int hmc_rows(void *h, size_t a, size_t b, void *o, size_t c, size_t d, void *s) { return mmcmc_hmc_run_rows((mmcmc_hmc *)h, a, b, o, c, d, s); }
-int hmc_state(void *h, void *o) { return mmcmc_hmc_state((mmcmc_hmc *)h, o); }
-
 } // namespace
 
 extern "C" {
@@ -191,8 +180,7 @@ int mmcmc_mh_run_progress(mmcmc_mh *h, size_t n_collect, size_t n_discard, size_
     size_t c = 0;
     int dim = 0, dtype = 0, device = 0;
     MMP(mmcmc_mh_shape(h, &c, &dim, &dtype, &device));
-    const FixedOps ops{mh_rows, mh_state, true};
-    return fixed_run_progress(h, ops, c, dim, dtype, device, n_collect, n_discard, every, cb, user, out, out_is_device, stats,
+    return fixed_run_progress(h, mm_ops_mh, c, dim, dtype, device, n_collect, n_discard, every, cb, user, out, out_is_device, stats,
                               tracker_out, stream);
 }
 
@@ -202,8 +190,7 @@ int mmcmc_hmc_run_progress(mmcmc_hmc *h, size_t n_collect, size_t n_discard, siz
     size_t c = 0;
     int dim = 0, dtype = 0, device = 0;
     MMP(mmcmc_hmc_shape(h, &c, &dim, &dtype, &device));
-    const FixedOps ops{hmc_rows, hmc_state, false};
-    return fixed_run_progress(h, ops, c, dim, dtype, device, n_collect, n_discard, every, cb, user, out, out_is_device, stats,
+    return fixed_run_progress(h, mm_ops_hmc, c, dim, dtype, device, n_collect, n_discard, every, cb, user, out, out_is_device, stats,
                               tracker_out, stream);
 }
 
@@ -227,12 +214,12 @@ int mmcmc_nuts_run_progress(mmcmc_nuts *h, size_t n_collect, size_t n_discard, s
     MMP(mmcmc_tracker_create(&tr.t, n_chains, dim, device));
     /* pos_0 = the position the chain starts from (init_chain does not move it, nuts.rs:478-486) */
     std::vector<unsigned char> st0(n_chains * dim * esz);
-    MMP(mmcmc_nuts_state(h, st0.data()));
+    MMP(mm_ops_nuts.state(h, st0.data()));
     MMP(mmcmc_tracker_init_last(tr.t, st0.data(), 0, dtype, stream));
     /* all n_discard + n_collect states of every chain, then the trackers in the order the chains produced them */
     DevBuf all, sample;
     MMP_HIP(hipMalloc(&all.p, n_chains * total * dim * esz));
-    MMP(mmcmc_nuts_run(h, n_collect, n_discard, all.p, 1, 2, stream));
+    MMP(mm_ops_nuts.run(h, n_collect, n_discard, all.p, nullptr, 2, stream));
     MMP(mm_nuts_draw_stats_window(h, n_discard, n_collect)); /* per-draw records, if recorded: of the sample's rows */
     if (every == 0)
         every = std::max<size_t>(1, (total + 9) / 10);

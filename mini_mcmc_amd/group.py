@@ -31,6 +31,22 @@ class _Group(K.Checkpointable):
     def _fn(self, name):
         return getattr(L.lib(), f"mmcmc_{self._prefix}_group_{name}")
 
+    def _open(self, target: Target, initial, devices, create, dtype=None):
+        """What the three constructors share: `initial` [n_chains, dim] as a contiguous float32 / float64 array (of `dtype`,
+        if given), the device list, the empty handle; then create(handle, target desc, init array, device array, n_devices)
+        -> status, the sampler's own mmcmc_*_group_create."""
+        init = np.ascontiguousarray(initial, dtype=dtype)
+        if init.dtype not in (np.float32, np.float64):
+            init = init.astype(np.float32)
+        self.n_chains, self.dim = init.shape
+        self.dtype = init.dtype.type
+        self.devices = [int(d) for d in devices]
+        self.target = target
+        dev = (C.c_int * len(self.devices))(*self.devices)
+        self._h = C.c_void_p()
+        d = target.desc()
+        L.check(create(C.byref(self._h), C.byref(d), init, dev, len(self.devices)), f"mmcmc_{self._prefix}_group_create")
+
     def set_chain_offset(self, first_global_chain: int):
         L.check(self._fn("set_chain_offset")(self._h, int(first_global_chain)), "group_set_chain_offset")
         return self
@@ -145,19 +161,8 @@ class HMCGroup(_Group):
     _cprefix, _ckpt_sampler = "hmc_group", "hmc"
 
     def __init__(self, target: Target, initial_positions, step_size: float, n_leapfrog: int, devices=(0,)):
-        init = np.ascontiguousarray(initial_positions)
-        if init.dtype not in (np.float32, np.float64):
-            init = init.astype(np.float32)
-        self.n_chains, self.dim = init.shape
-        self.dtype = init.dtype.type
-        self.devices = [int(d) for d in devices]
-        self.target = target
-        dev = (C.c_int * len(self.devices))(*self.devices)
-        self._h = C.c_void_p()
-        d = target.desc()
-        st = L.lib().mmcmc_hmc_group_create(C.byref(self._h), C.byref(d), init.ctypes.data, self.n_chains, float(step_size),
-                                            int(n_leapfrog), L.F32 if self.dtype == np.float32 else L.F64, dev, len(self.devices))
-        L.check(st, "mmcmc_hmc_group_create")
+        self._open(target, initial_positions, devices, lambda h, d, x, dev, n: L.lib().mmcmc_hmc_group_create(
+            h, d, x.ctypes.data, self.n_chains, float(step_size), int(n_leapfrog), L.F32 if self.dtype == np.float32 else L.F64, dev, n))
 
     def set_seed(self, seed: int) -> "HMCGroup":
         L.check(L.lib().mmcmc_hmc_group_seed(self._h, int(seed)), "mmcmc_hmc_group_seed")
@@ -201,19 +206,9 @@ class MetropolisHastingsGroup(_Group):
     _cprefix, _ckpt_sampler = "mh_group", "mh"
 
     def __init__(self, target: Target, proposal: IsotropicGaussian, initial_states, devices=(0,)):
-        init = np.ascontiguousarray(initial_states)
-        if init.dtype not in (np.float32, np.float64):
-            init = init.astype(np.float32)
-        self.n_chains, self.dim = init.shape
-        self.dtype = init.dtype.type
-        self.devices = [int(d) for d in devices]
-        self.target = target
-        dev = (C.c_int * len(self.devices))(*self.devices)
-        self._h = C.c_void_p()
-        d, p = target.desc(), proposal.proposal_desc()
-        st = L.lib().mmcmc_mh_group_create(C.byref(self._h), C.byref(d), C.byref(p), init.ctypes.data, self.n_chains,
-                                           L.F32 if self.dtype == np.float32 else L.F64, dev, len(self.devices))
-        L.check(st, "mmcmc_mh_group_create")
+        p = proposal.proposal_desc()
+        self._open(target, initial_states, devices, lambda h, d, x, dev, n: L.lib().mmcmc_mh_group_create(
+            h, d, C.byref(p), x.ctypes.data, self.n_chains, L.F32 if self.dtype == np.float32 else L.F64, dev, n))
 
     def seed(self, seed: int) -> "MetropolisHastingsGroup":
         L.check(L.lib().mmcmc_mh_group_seed(self._h, int(seed)), "mmcmc_mh_group_seed")
@@ -237,18 +232,10 @@ class NUTSGroup(_Group):
     _cprefix, _ckpt_sampler = "nuts_group", "nuts"
 
     def __init__(self, target: Target, initial_positions, target_accept_p: float, mode: int = 0, devices=(0,)):
-        init = np.ascontiguousarray(initial_positions, dtype=np.float64)
-        self.n_chains, self.dim = init.shape
         self.mode = int(mode)
-        self.dtype = np.float64 if self.mode == 2 else np.float32
-        self.devices = [int(d) for d in devices]
-        self.target = target
-        dev = (C.c_int * len(self.devices))(*self.devices)
-        self._h = C.c_void_p()
-        d = target.desc()
-        st = L.lib().mmcmc_nuts_group_create(C.byref(self._h), C.byref(d), init.ctypes.data_as(C.POINTER(C.c_double)), self.n_chains,
-                                             float(target_accept_p), self.mode, dev, len(self.devices))
-        L.check(st, "mmcmc_nuts_group_create")
+        self._open(target, initial_positions, devices, lambda h, d, x, dev, n: L.lib().mmcmc_nuts_group_create(
+            h, d, x.ctypes.data_as(C.POINTER(C.c_double)), self.n_chains, float(target_accept_p), self.mode, dev, n), dtype=np.float64)
+        self.dtype = np.float64 if self.mode == 2 else np.float32  # of the sample; the initial positions are always doubles
 
     def set_seed(self, seed: int) -> "NUTSGroup":
         L.check(L.lib().mmcmc_nuts_group_seed(self._h, int(seed)), "mmcmc_nuts_group_seed")

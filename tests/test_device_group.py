@@ -335,3 +335,163 @@ def test_group_cross_chain_sums_keep_their_digits_on_an_offset_target(O):
     np.testing.assert_allclose(r1, ro, rtol=1e-4)
     np.testing.assert_allclose(e1, eo, rtol=5e-3)
     assert np.all(np.abs(r1 - 1.0) < 0.05)  # a converged unit Gaussian: with the digits lost this is far off or NaN
+
+
+# ---------------------------------------------------------------- every group entry point, by name (no device)
+def _declared_group_functions():
+    """every mmcmc_*group_* function include/mmcmc.h declares, taken from the header so that none is forgotten"""
+    import os
+    import re
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "include", "mmcmc.h")).read()
+    return sorted(set(re.findall(r"^int\s+(mmcmc_\w*group_\w+)\s*\(", text, flags=re.M)))
+
+
+def test_every_group_entry_point_refuses_a_null_handle():
+    import re
+
+    import mini_mcmc_amd
+    from mini_mcmc_amd import _lib as L
+
+    lib = mini_mcmc_amd.lib()
+    names = [n for n in _declared_group_functions() if re.match(r"mmcmc_(hmc|mh|nuts)_group_", n) and not n.endswith("_create")]
+    assert len(names) >= 54 and {n.split("_")[1] for n in names} == {"hmc", "mh", "nuts"}
+    for name in names:
+        args = L.SIGNATURES[name][1]
+        assert args[0] is C.c_void_p, name  # the handle
+        rest = [0.0 if t is C.c_double else 0 if t in (C.c_int, C.c_size_t, C.c_uint64) else None for t in args[1:]]
+        assert getattr(lib, name)(None, *rest) == L.ERR_INVALID_ARG, name
+
+
+def test_exported_group_symbols_are_the_declared_ones():
+    import os
+    import re
+    import shutil
+    import subprocess
+
+    from mini_mcmc_amd import _lib as L
+
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    r = subprocess.run([nm, "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    exported = {line.split()[-1] for line in r.stdout.splitlines() if line.split() and re.search(r"_group_", line.split()[-1])}
+    declared = _declared_group_functions()
+    assert len(declared) >= 58 and exported == set(declared), sorted(exported ^ set(declared))
+
+
+# ---------------------------------------------------------------- the entry points no other test calls on a group (GPU)
+# devices = [0, 0, 0] with 7 chains: shards of 3 / 2 / 2 chains.  A group and a single handle get the same calls; samples,
+# states and counts must be bit-equal, and a refused call must leave everything as it was.
+PIN_DEVICES, PIN_CHAINS, PIN_COLLECT, PIN_DISCARD = [0, 0, 0], 7, 6, 2
+
+
+def _iteration_round_trip(g, one, run_g, run_one):
+    """set_chain_offset / set_iteration / stream_position on a group against the single handle, then a run"""
+    from mini_mcmc_amd import _lib as L
+
+    seed = one.stream_position()[0]
+    g.set_chain_offset(5)
+    one.set_chain_offset(5)
+    g.set_iteration(1000)
+    one.set_iteration(1000)
+    assert g.stream_position() == (seed, 5, 1000) == one.stream_position()  # first_global_chain = the user's offset
+    assert getattr(L.lib(), f"mmcmc_{g._cprefix}_set_iteration")(g._h, 2 ** 32) == L.ERR_INVALID_ARG
+    assert g.stream_position() == (seed, 5, 1000)
+    assert np.array_equal(run_g(), run_one())
+    assert np.array_equal(g.state(), one.positions() if one._ckpt_sampler == "nuts" else one.state())
+    assert g.stream_position() == one.stream_position()
+
+
+@pytest.mark.gpu
+def test_hmc_group_setters_and_iteration_equal_the_single_handle():
+    from mini_mcmc_amd import _lib as L
+    from mini_mcmc_amd.core import init_with_seed
+    from mini_mcmc_amd.distributions import RosenbrockND
+    from mini_mcmc_amd.group import HMCGroup
+    from mini_mcmc_amd.hmc import HMC
+
+    init = init_with_seed(PIN_CHAINS, 3, 42, np.float32)
+    one = HMC(RosenbrockND(3), init, 0.032, 10).set_seed(42)
+    g = HMCGroup(RosenbrockND(3), init, 0.032, 10, devices=PIN_DEVICES).set_seed(42)
+    assert [s[2] for s in g.shards()] == [3, 2, 2] and [s[1] for s in g.shards()] == [0, 3, 5]
+    for h in (one, g):
+        h.step_size = 0.021
+    assert np.array_equal(g.run(PIN_COLLECT, PIN_DISCARD), one.run(PIN_COLLECT, PIN_DISCARD))
+    assert np.array_equal(g.accept_counts, one.accept_counts) and np.array_equal(g.state(), one.state())
+    for h in (one, g):
+        h.n_leapfrog = 7
+    assert (g.step_size, g.n_leapfrog) == (0.021, 7) == (one.step_size, one.n_leapfrog)
+    assert np.array_equal(g.run(PIN_COLLECT, 0), one.run(PIN_COLLECT, 0))
+    assert np.array_equal(g.accept_counts, one.accept_counts) and np.array_equal(g.state(), one.state())
+    before = g.state()
+    assert L.lib().mmcmc_hmc_group_set_step_size(g._h, 0.0) == L.ERR_INVALID_ARG
+    assert L.lib().mmcmc_hmc_group_set_n_leapfrog(g._h, -1) == L.ERR_INVALID_ARG
+    assert (g.step_size, g.n_leapfrog) == (0.021, 7) and np.array_equal(g.state(), before)
+    _iteration_round_trip(g, one, lambda: g.run(PIN_COLLECT, PIN_DISCARD), lambda: one.run(PIN_COLLECT, PIN_DISCARD))
+    assert np.array_equal(g.accept_counts, one.accept_counts)
+
+
+@pytest.mark.gpu
+def test_mh_group_setters_and_iteration_equal_the_single_handle():
+    from mini_mcmc_amd import _lib as L
+    from mini_mcmc_amd.core import init_with_seed
+    from mini_mcmc_amd.distributions import Gaussian2D, IsotropicGaussian
+    from mini_mcmc_amd.group import MetropolisHastingsGroup
+    from mini_mcmc_amd.metropolis_hastings import MetropolisHastings
+
+    init = init_with_seed(PIN_CHAINS, 2, 7, np.float64)
+    tgt = Gaussian2D([0.0, 1.0], [[4.0, 2.0], [2.0, 3.0]])
+    one = MetropolisHastings(tgt, IsotropicGaussian(1.0), init).seed(5)
+    g = MetropolisHastingsGroup(tgt, IsotropicGaussian(1.0), init, devices=PIN_DEVICES).seed(5)
+    for h in (one, g):
+        h.proposal_std = 0.37
+    assert g.proposal_std == 0.37 == one.proposal_std
+    assert np.array_equal(g.run(PIN_COLLECT, PIN_DISCARD), one.run(PIN_COLLECT, PIN_DISCARD))
+    assert np.array_equal(g.accept_counts, one.accept_counts) and np.array_equal(g.state(), one.state())
+    before = g.state()
+    assert L.lib().mmcmc_mh_group_set_proposal_std(g._h, 0.0) == L.ERR_INVALID_ARG
+    assert g.proposal_std == 0.37 and np.array_equal(g.state(), before)
+    _iteration_round_trip(g, one, lambda: g.run(PIN_COLLECT, PIN_DISCARD), lambda: one.run(PIN_COLLECT, PIN_DISCARD))
+    assert np.array_equal(g.accept_counts, one.accept_counts)
+
+
+@pytest.mark.gpu
+def test_nuts_group_setters_adaptation_and_iteration_equal_the_single_handle():
+    from mini_mcmc_amd import _lib as L
+    from mini_mcmc_amd import checkpoint as K
+    from mini_mcmc_amd.core import init_with_seed
+    from mini_mcmc_amd.distributions import RosenbrockND
+    from mini_mcmc_amd.group import NUTSGroup
+    from mini_mcmc_amd.nuts import NUTS
+
+    lib = L.lib()
+    init = init_with_seed(PIN_CHAINS, 3, 42) * 0.5
+    one = NUTS(RosenbrockND(3), init, 0.8, mode=0).set_seed(42)
+    g = NUTSGroup(RosenbrockND(3), init, 0.8, mode=0, devices=PIN_DEVICES).set_seed(42)
+    one.set_target_accept_p(0.65)
+    assert lib.mmcmc_nuts_group_set_target_accept_p(g._h, 0.65) == L.OK
+    one.set_max_depth(4)
+    g.set_max_depth(4)
+    assert K._fields(g) == {"target_accept_p": 0.65, "max_depth": 4} == K._fields(one)
+    assert np.array_equal(g.run(PIN_COLLECT, PIN_DISCARD), one.run(PIN_COLLECT, PIN_DISCARD))
+    assert np.array_equal(g.state(), one.positions()) and np.array_equal(g.leapfrog_counts(), one.leapfrog_counts())
+    adapt = K.adapt_array(g)
+    assert np.array_equal(adapt, K.adapt_array(one)) and np.all(np.isfinite(adapt))
+    # refusals: nothing changes
+    assert lib.mmcmc_nuts_group_set_target_accept_p(g._h, 1.0) == L.ERR_INVALID_ARG
+    assert lib.mmcmc_nuts_group_set_draw_stats(g._h, 1) == L.ERR_UNSUPPORTED
+    assert K._fields(g) == {"target_accept_p": 0.65, "max_depth": 4}
+    bad = adapt.copy()
+    bad[:, 0] *= 0.5  # every row differs from what the shards hold ...
+    bad[PIN_CHAINS - 1, 2] = np.inf  # ... and one value in the LAST shard's rows is not finite: no shard may change
+    assert lib.mmcmc_nuts_group_set_adapt_state(g._h, bad.ctypes.data_as(C.POINTER(C.c_double))) == L.ERR_INVALID_ARG
+    assert np.array_equal(K.adapt_array(g), adapt)
+    # an accepted adaptation state, then the iteration round trip and a run
+    new = adapt.copy()
+    new[:, 0] *= 0.5
+    g.set_adapt_state(new)
+    one.set_adapt_state(new)
+    assert np.array_equal(K.adapt_array(g), K.adapt_array(one))
+    _iteration_round_trip(g, one, lambda: g.run(PIN_COLLECT, 0), lambda: one.run(PIN_COLLECT, 0))
+    assert np.array_equal(g.leapfrog_counts(), one.leapfrog_counts()) and np.array_equal(K.adapt_array(g), K.adapt_array(one))
