@@ -429,16 +429,18 @@ int sampler_destroy(Sampler *s)
     return MMCMC_OK;
 }
 
-/* mm_tile<T, D>::lds_bytes_table + lds_bytes_per_wave for a dimension known only at run time (one wave per workgroup):
- * must mirror mm_kernels.h (mm_tile_default / mm_tile_t) */
+/* mm_tile<T, D>::lds_bytes_table + lds_bytes_per_wave for a dimension known only at run time (one wave per workgroup), by
+ * the functions mm_kernels.h defines mm_tile through */
 static size_t mm_tile_lds_bytes_rt(size_t esz, int D)
 {
-    const int target = esz == 4 ? 96 : 48;
-    const int tile_t = (target / D) >= 2 ? ((target / D) & ~1) : 1;
-    const int run = tile_t * D, epl = (int)(16 / esz);
-    const int stride = (run % epl) == 0 ? run + epl : (run | 1);
-    return (esz == 4 ? (size_t)MM_NOISE_TABLE_BYTES : 0) + (size_t)64 * stride * esz;
+    return mm_tile_lds_bytes_table(esz) + mm_tile_lds_bytes_per_wave(esz, D, mm_tile_default_t(esz, D));
 }
+static_assert(mm_tile_lds_bytes_table(4) + mm_tile_lds_bytes_per_wave(4, 3, mm_tile_default_t(4, 3)) ==
+                      mm_tile<float, 3>::lds_bytes_table + mm_tile<float, 3>::lds_bytes_per_wave &&
+                  mm_tile_lds_bytes_per_wave(8, 9, mm_tile_default_t(8, 9)) == mm_tile<double, 9>::lds_bytes_per_wave &&
+                  mm_tile_lds_bytes_per_wave(4, 32, mm_tile_default_t(4, 32)) == mm_tile<float, 32>::lds_bytes_per_wave &&
+                  mm_tile<float, 3>::lds_bytes_per_wave == 25600 && mm_tile<double, 32>::lds_bytes_per_wave == 17408,
+              "the run-time tile rule is the templates'");
 
 /* the fields every kernel argument struct has under the same name, from the run's mm_run_args */
 template <class Q, class T> Q shared_args(const mm_run_args<T> &a)

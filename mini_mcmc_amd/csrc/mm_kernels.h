@@ -73,24 +73,33 @@ __device__ __forceinline__ void mm_sched_at(const mm_run_args<T> &a, const mm_sc
 
 constexpr int mm_gcd_c(int a, int b) { return b == 0 ? a : mm_gcd_c(b, a % b); }
 
+/* The tile rule as functions of the element size and the dimension, so that the host sizes the LDS of a kernel whose
+ * dimension it learns at run time (a run-time compiled unit) by the rule the templates below are defined through.
+ * Row pitch of the staged tile of `run` elements per chain: when a chain's run is a whole number of 16-byte pieces the
+ * pitch keeps every piece 16-byte aligned (one ds_read_b128 per piece in the flush; the lane-strided staging writes then
+ * meet a 4-way bank conflict, which costs a few LDS cycles per transition); otherwise odd => conflict-free both ways */
+constexpr int mm_tile_epl(size_t esz) { return 16 / (int)esz; }
+constexpr int mm_tile_stride(size_t esz, int run) { return (run % mm_tile_epl(esz)) == 0 ? run + mm_tile_epl(esz) : (run | 1); }
+constexpr size_t mm_tile_lds_bytes_per_wave(size_t esz, int D, int tile_t) { return (size_t)64 * mm_tile_stride(esz, tile_t * D) * esz; }
+/* f32 kernels keep the tables of the normal draw and of ln u (mm_rng.h) in LDS, once per block, before the tiles */
+constexpr size_t mm_tile_lds_bytes_table(size_t esz) { return esz == 4 ? (size_t)MM_NOISE_TABLE_BYTES : 0; }
+/* about 96 f32 (48 f64) elements per chain => 25.6 KB of LDS per wave; even whenever possible: the kernels advance
+ * two transitions at a time */
+constexpr int mm_tile_target(size_t esz) { return esz == 4 ? 96 : 48; }
+constexpr int mm_tile_default_t(size_t esz, int D) { return (mm_tile_target(esz) / D) >= 2 ? ((mm_tile_target(esz) / D) & ~1) : 1; }
+
 /* TILE_T iterations of 64 chains staged per flush */
 template <class T, int D, int TILE_T> struct mm_tile_t {
     static constexpr int tile_t = TILE_T;
     static constexpr int run = tile_t * D;
-    /* row pitch of the staged tile.  When a chain's run is a whole number of 16-byte pieces the pitch keeps every
-     * piece 16-byte aligned (one ds_read_b128 per piece in the flush; the lane-strided staging writes then meet a
-     * 4-way bank conflict, which costs a few LDS cycles per transition); otherwise odd => conflict-free both ways */
-    static constexpr int epl = 16 / (int)sizeof(T);
-    static constexpr int stride = (run % epl) == 0 ? run + epl : (run | 1);
-    static constexpr size_t lds_bytes_per_wave = (size_t)64 * stride * sizeof(T);
-    /* f32 kernels keep the tables of the normal draw and of ln u (mm_rng.h) in LDS, once per block, before the tiles */
-    static constexpr size_t lds_bytes_table = (sizeof(T) == 4) ? (size_t)MM_NOISE_TABLE_BYTES : 0;
+    static constexpr int epl = mm_tile_epl(sizeof(T));
+    static constexpr int stride = mm_tile_stride(sizeof(T), run);
+    static constexpr size_t lds_bytes_per_wave = mm_tile_lds_bytes_per_wave(sizeof(T), D, TILE_T);
+    static constexpr size_t lds_bytes_table = mm_tile_lds_bytes_table(sizeof(T));
 };
-/* about 96 f32 (48 f64) elements per chain => 25.6 KB of LDS per wave; even whenever possible: the kernels advance
- * two transitions at a time */
 template <class T, int D> struct mm_tile_default {
-    static constexpr int target = (sizeof(T) == 4) ? 96 : 48;
-    static constexpr int tile_t = (target / D) >= 2 ? ((target / D) & ~1) : 1;
+    static constexpr int target = mm_tile_target(sizeof(T));
+    static constexpr int tile_t = mm_tile_default_t(sizeof(T), D);
 };
 template <class T, int D> struct mm_tile : mm_tile_t<T, D, mm_tile_default<T, D>::tile_t> {};
 

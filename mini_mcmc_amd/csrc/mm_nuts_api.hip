@@ -27,8 +27,56 @@
 #include "mm_tuning.h"
 #include "mm_rtc.h"
 #include "mm_params.h"
+#include "mm_nuts_plan.h"
+
+static_assert(MM_NUTS_JMAX == MM_NUTS_PLAN_JMAX && MM_LGQ_ID_BITS == MM_NUTS_PLAN_ID_BITS, "mm_nuts_plan.h's copies of the kernel headers' constants");
+static_assert(MM_NMETRIC_NONE == MM_METRIC_NONE && MM_NMETRIC_DIAG == MM_METRIC_DIAG && MM_NMETRIC_DENSE == MM_METRIC_DENSE &&
+                  MM_NVAR_UNIT == mm_metric_variant,
+              "mm_nuts_plan.h's metric kinds are mm_metric_host.h's; a handle with a metric is on variant 7");
+/* the layout rules as functions of run-time sizes (mm_kernels.h, mm_nuts_kernels.h) against the templates' values */
+static_assert(mm_nuts_stack_bytes(4, 8, 3) == mm_nuts_stack_layout<float, double, 3>::bytes && mm_nuts_stack_layout<float, double, 3>::bytes == 43008 &&
+                  mm_nuts_stack_bytes(4, 4, 9) == mm_nuts_stack_layout<float, float, 9>::bytes &&
+                  mm_nuts_stack_bytes(8, 8, 32) == mm_nuts_stack_layout<double, double, 32>::bytes &&
+                  mm_tile_lds_bytes_per_wave(4, 9, mm_tile_default_t(4, 9)) == mm_tile<float, 9>::lds_bytes_per_wave &&
+                  mm_tile_lds_bytes_per_wave(8, 32, mm_tile_default_t(8, 32)) == mm_tile<double, 32>::lds_bytes_per_wave,
+              "the run-time layout rules are the templates'");
 
 namespace {
+
+/* a measurement knob (mm_tuning.h): absent in an ordinary build */
+inline mm_knob knob(const char *name)
+{
+    mm_knob k;
+    if (const char *ev = mm_tuning_env(name)) {
+        k.set = true;
+        k.value = atoi(ev);
+    }
+    return k;
+}
+
+/* the fields every NUTS argument struct has under the same name, from the run's mm_nuts_args */
+template <class Q, class A> Q shared_nuts_args(const A &a)
+{
+    Q q;
+    q.state = a.state;
+    q.adapt = a.adapt;
+    q.out = a.out;
+    q.n_leapfrog = a.n_leapfrog;
+    q.depth_hist = a.depth_hist;
+    q.n_chains = a.n_chains;
+    q.seed = a.seed;
+    q.chain_offset = a.chain_offset;
+    q.n_total = a.n_total;
+    q.m0 = a.m0;
+    q.n_pre = a.n_pre;
+    q.n_rec = a.n_rec;
+    q.write_initial = a.write_initial;
+    q.out_t0 = a.out_t0;
+    q.n_discard = a.n_discard;
+    q.max_depth = a.max_depth;
+    q.target_accept_p = a.target_accept_p;
+    return q;
+}
 
 /* 0: normal; 1: inside the self-test of a run-time compiled unit; 2: create without run-time compiled built-in units */
 thread_local int g_rtc_create_mode = 0;
@@ -42,19 +90,24 @@ struct NutsBase {
     virtual int set_adapt_state(const double *in) = 0;
     virtual int leapfrog_counts(uint64_t *out) = 0;
     virtual int depth_histogram(uint32_t *out) = 0;
-    virtual int set_variant(int v) = 0;
     virtual int set_metric(bool dense, const double *values) = 0;
     virtual int set_draw_stats(bool on) = 0;
     virtual int draw_stats(mmcmc_nuts_draw *out, int out_is_device, size_t *n_rows) = 0;
     virtual int draw_stats_window(size_t first, size_t rows) = 0;
+    mm_nuts_caps caps; /* what setup() found for the handle: the facts the kernel-path rule (mm_nuts_plan.h) works on */
+    int set_variant(int v)
+    {
+        const int st = mm_nuts_variant_status(caps, met.kind, recording, v);
+        if (st == MMCMC_OK) /* with a metric or while recording this is 7, which the handle is on */
+            variant = v;
+        return st;
+    }
     mm_metric_record met; /* the metric that is set (mmcmc_nuts_set_metric, _set_metric_dense; mm_metric_host.h) */
     /* per-draw statistics (mmcmc_nuts_set_draw_stats): while on the handle runs a stats unit, variant 7, like a handle with a
      * metric.  The variant to return to is kept once: by `met` while a metric is set, else here. */
     bool recording = false;
     int variant_before_recording = 0;
-    int variant = 0; /* 0: one chain per lane, lanes in step; 4: one chain per lane, asynchronous lanes (default for
-                      * dim <= 8); 1: lane-group / MFMA (mm_nuts_lg.h); 2: + tree-depth compaction, one
-                        launch per level; 3: + compaction by a persistent scheduler */
+    int variant = 0; /* MM_NVAR_* (mm_nuts_plan.h): always one mm_nuts_variant_status allows on this handle */
     int compaction_start = 5; /* variants 2, 3: doublings below this run before the first compaction */
     bool compaction_auto = true; /* variant 3: choose it from the depths seen so far (until set_compaction is called) */
     int compaction_groups = 0; /* variant 2: chain groups with their own launch sequence (0 = choose) */
@@ -121,7 +174,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
     unsigned int n_launches_run = 0; /* sampling launches of the current run() (reported by timing()) */
     int auto_level = -1;             /* first compaction level chosen from the depth histogram, once it is known */
     size_t c_pad = 0;
-    static constexpr int kMaxGroups = 16;
+    static constexpr int kMaxGroups = MM_NUTS_LG_MAX_GROUPS;
     hipStream_t lg_streams[kMaxGroups] = {};
     hipEvent_t lg_fork = nullptr, lg_join[kMaxGroups] = {};
 
@@ -165,18 +218,70 @@ template <class TT, class ST> struct Nuts : NutsBase {
      * take as stack area per wave and (lanes in step) as dynamic LDS */
     static void unit_sizes(size_t D, size_t *stack_bytes, size_t *tile_lds)
     {
-        const size_t a16 = 15;
-        *stack_bytes = (((size_t)MM_NUTS_JMAX * 3 * D * 64 * sizeof(TT) + a16) / 16 * 16) +
-                       (((size_t)MM_NUTS_JMAX * 64 * sizeof(ST) + a16) / 16 * 16) +
-                       (((size_t)MM_NUTS_JMAX * 3 * 64 * sizeof(uint32_t) + a16) / 16 * 16);
-        const int target = sizeof(TT) == 4 ? 96 : 48;
-        const int tile_t = (target / (int)D) >= 2 ? ((target / (int)D) & ~1) : 1;
-        const int run_len = tile_t * (int)D, epl = (int)(16 / sizeof(TT));
-        const int stride = (run_len % epl) == 0 ? run_len + epl : (run_len | 1);
-        *tile_lds = ((size_t)64 * stride * sizeof(TT) + 15) / 16 * 16; /* must mirror mm_kernels.h (mm_tile_default) */
+        *stack_bytes = mm_nuts_stack_bytes(sizeof(TT), sizeof(ST), (int)D);
+        *tile_lds = (mm_tile_lds_bytes_per_wave(sizeof(TT), (int)D, mm_tile_default_t(sizeof(TT), (int)D)) + 15) / 16 * 16;
     }
 
-    static constexpr int type_mode_of = std::is_same<TT, double>::value ? 2 : (std::is_same<ST, double>::value ? 0 : 1);
+    static constexpr int type_mode = std::is_same<TT, double>::value ? 2 : (std::is_same<ST, double>::value ? 0 : 1);
+    static constexpr ST eps_tol = sizeof(ST) == 4 ? (ST)1.1920929e-7 : (ST)2.220446049250313e-16; /* T::epsilon() */
+    /* NUTSChain::new (nuts.rs:415-433): epsilon = -1 (sentinel: no search yet), epsilon_bar = 1, h_bar = 0, mu = ln 10 */
+    static void fresh_adapt(std::vector<mm_nuts_adapt<ST>> &ad)
+    {
+        for (auto &a : ad) {
+            a.epsilon = (ST)-1;
+            a.epsilon_bar = (ST)1;
+            a.h_bar = (ST)0;
+            a.mu = (ST)std::log(10.0);
+        }
+    }
+
+    /* what a run works on: the handle's own buffers and stream position (run()), or those of unit_verified's probe */
+    struct Where {
+        TT *state;
+        mm_nuts_adapt<ST> *adapt;
+        TT *out;
+        unsigned long long *n_leapfrog;
+        unsigned int *depth_hist;
+        unsigned char *scratch;
+        size_t n_chains;
+        uint64_t seed, chain_offset;
+        uint32_t m0;
+        int max_depth;
+        double target_accept_p;
+        bool stack_in_lds;
+    };
+    /* both argument blocks of the run `s` (mm_nuts_step_plan) there */
+    void fill_args(const Where &w, const mm_nuts_steps &s, size_t n_discard, mm_nuts_init_args<TT, ST> *ia, mm_nuts_args<TT, ST> *a) const
+    {
+        ia->P = P;
+        ia->state = w.state;
+        ia->adapt = w.adapt;
+        ia->n_chains = w.n_chains;
+        ia->seed = w.seed;
+        ia->chain_offset = w.chain_offset;
+        ia->eps_tol = eps_tol;
+        a->P = P;
+        a->state = w.state;
+        a->adapt = w.adapt;
+        a->out = w.out;
+        a->n_leapfrog = w.n_leapfrog;
+        a->depth_hist = w.depth_hist;
+        a->n_chains = w.n_chains;
+        a->seed = w.seed;
+        a->chain_offset = w.chain_offset;
+        a->n_total = s.n_rows;
+        a->m0 = w.m0;
+        a->n_pre = s.n_pre;
+        a->n_rec = s.n_rec;
+        a->write_initial = s.write_initial;
+        a->out_t0 = 0;
+        a->n_discard = (unsigned int)n_discard;
+        a->max_depth = w.max_depth;
+        a->target_accept_p = (ST)w.target_accept_p;
+        a->stack_in_lds = w.stack_in_lds ? 1 : 0;
+        a->async_batch = 0;
+        a->scratch = w.scratch;
+    }
 
     /* One launch of a kernel of a metric unit or of a stats unit: init_chain (which = 1), a run by the pair kernel (which = 2:
      * what handles launch) or with the lanes in step (which = 0: the second opinion of unit_verified).  The argument block is `a`
@@ -201,7 +306,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
             push(met + mm_tri_len((size_t)dim));
         if (stats)
             push(rec);
-        return mm_rtc_launch_nuts(unit, type_mode_of, which, block, n, (unsigned int)((a.n_chains + 63) / 64), lds, st);
+        return mm_rtc_launch_nuts(unit, type_mode, which, block, n, (unsigned int)((a.n_chains + 63) / 64), lds, st);
     }
     hipError_t unit_init(const mm_user_target *unit, int metric_kind, const mm_nuts_init_args<TT, ST> &ia, const TT *met, hipStream_t st)
     {
@@ -245,12 +350,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
         if (metric_kind != MM_METRIC_NONE && !metric_image(dense, (dense ? mm_probe_chol(D) : mm_probe_scale(D)).data(), met))
             return false;
         std::vector<mm_nuts_adapt<ST>> ad0(n);
-        for (auto &a : ad0) {
-            a.epsilon = (ST)-1;
-            a.epsilon_bar = (ST)1;
-            a.h_bar = (ST)0;
-            a.mu = (ST)std::log(10.0);
-        }
+        fresh_adapt(ad0);
         struct Dev {
             TT *x = nullptr, *out = nullptr, *met = nullptr;
             mm_nuts_adapt<ST> *ad = nullptr;
@@ -278,36 +378,11 @@ template <class TT, class ST> struct Nuts : NutsBase {
                 hipMemcpy(d.x, x0.data(), n * D * sizeof(TT), hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(d.ad, ad0.data(), n * sizeof(mm_nuts_adapt<ST>), hipMemcpyHostToDevice) != hipSuccess)
                 return false;
+            /* run_progress' stepping: all ten transitions, the last five recorded; from step 0 of the probe's own stream */
             mm_nuts_init_args<TT, ST> ia;
-            ia.P = P;
-            ia.state = d.x;
-            ia.adapt = d.ad;
-            ia.n_chains = n;
-            ia.seed = 0x5eedull;
-            ia.chain_offset = 0;
-            ia.eps_tol = sizeof(ST) == 4 ? (ST)1.1920929e-7 : (ST)2.220446049250313e-16;
             mm_nuts_args<TT, ST> a;
-            a.P = P;
-            a.state = d.x;
-            a.adapt = d.ad;
-            a.out = d.out;
-            a.n_leapfrog = nullptr;
-            a.depth_hist = nullptr;
-            a.n_chains = n;
-            a.seed = ia.seed;
-            a.chain_offset = 0;
-            a.n_total = nc;
-            a.m0 = 0;
-            a.n_pre = (unsigned int)nd; /* run_progress' stepping: all ten transitions, the last five recorded */
-            a.n_rec = (unsigned int)nc;
-            a.write_initial = 0;
-            a.out_t0 = 0;
-            a.n_discard = (unsigned int)nd;
-            a.max_depth = 10;
-            a.target_accept_p = (ST)0.8;
-            a.stack_in_lds = 0;
-            a.async_batch = 0;
-            a.scratch = d.scratch;
+            fill_args(Where{d.x, d.ad, d.out, nullptr, nullptr, d.scratch, n, 0x5eedull, 0, 0, 10, 0.8, false},
+                      mm_nuts_step_plan(nc, nd, 1, dim, 0), nd, &ia, &a);
             return unit_init(unit, metric_kind, ia, d.met, stream) == hipSuccess && unit_run(unit, metric_kind, a, which, d.met, stats, d.rec, stream) == hipSuccess &&
                    hipStreamSynchronize(stream) == hipSuccess &&
                    hipMemcpy(got.data(), d.out, got.size() * sizeof(TT), hipMemcpyDeviceToHost) == hipSuccess &&
@@ -484,14 +559,13 @@ template <class TT, class ST> struct Nuts : NutsBase {
                 k = &tab[i];
         generic_ok = mm_generic_kind_ok(t->kind) && t->dim >= 1;
         bool builtin_user = false;
-        const int create_mode = std::is_same<TT, double>::value ? 2 : (std::is_same<ST, double>::value ? 0 : 1);
         if (t->kind < MM_USER_KIND_BASE && !k && generic_ok && t->dim <= 32 && g_rtc_create_mode != 2) {
             /* a built-in target at a dimension without a compiled instance: its functor compiled into the one-chain-per-lane
              * kernels on first use (hipRTC, mm_rtc_builtin_nuts); NULL keeps the run-time-D kernel */
             DevGuard gb(device);
             user = mm_rtc_builtin_nuts(t->kind, t->dim);
             /* ... and only if the unit has this type mode's init and pair kernels (mm_rtc_nuts_usable) */
-            if (user && !mm_rtc_nuts_usable(user, create_mode))
+            if (user && !mm_rtc_nuts_usable(user, type_mode))
                 user = nullptr;
             builtin_user = user != nullptr;
         }
@@ -509,7 +583,7 @@ template <class TT, class ST> struct Nuts : NutsBase {
                 return MMCMC_ERR_INVALID_ARG; /* a kind that carries data: its functor is never run with P.mat == nullptr */
             if (!builtin_user) {
                 DevGuard gu(device);
-                if (!mm_rtc_nuts_usable(user, create_mode))
+                if (!mm_rtc_nuts_usable(user, type_mode))
                     return MMCMC_ERR_UNSUPPORTED; /* this dimension and precision need more registers than a lane has */
             }
             unit_sizes((size_t)t->dim, &user_stack_bytes, &user_lds);
@@ -541,14 +615,8 @@ template <class TT, class ST> struct Nuts : NutsBase {
             h[i] = (TT)init[i]; /* Vec<Vec<T>> -> backend float tensor (nuts.rs:411-413) */
         MM_HIP(hipMalloc((void **)&d_state, cd * sizeof(TT)));
         MM_HIP(hipMemcpy(d_state, h.data(), cd * sizeof(TT), hipMemcpyHostToDevice));
-        /* NUTSChain::new (nuts.rs:415-433): epsilon = -1 (sentinel), epsilon_bar = 1, h_bar = 0, mu = ln 10 */
         std::vector<mm_nuts_adapt<ST>> ad(n_chains);
-        for (auto &a : ad) {
-            a.epsilon = (ST)-1;
-            a.epsilon_bar = (ST)1;
-            a.h_bar = (ST)0;
-            a.mu = (ST)std::log(10.0);
-        }
+        fresh_adapt(ad);
         MM_HIP(hipMalloc((void **)&d_adapt, n_chains * sizeof(mm_nuts_adapt<ST>)));
         MM_HIP(hipMemcpy(d_adapt, ad.data(), n_chains * sizeof(mm_nuts_adapt<ST>), hipMemcpyHostToDevice));
         MM_HIP(hipMalloc((void **)&d_nlf, n_chains * sizeof(unsigned long long)));
@@ -565,12 +633,9 @@ template <class TT, class ST> struct Nuts : NutsBase {
                 MM_HIP(hipMalloc((void **)&d_scratch, waves * k->stack_bytes_per_wave));
             }
         } else if (user) {
-            variant = 7;
             const size_t waves0 = (n_chains + 63) / 64;
             MM_HIP(hipMalloc((void **)&d_scratch, waves0 * user_stack_bytes));
             stack_in_lds = false;
-        } else {
-            variant = 6;
         }
         if (std::is_same<TT, double>::value && std::is_same<ST, double>::value && t->kind == MMCMC_GAUSSIAN_ND) {
             int nl = 0;
@@ -590,54 +655,144 @@ template <class TT, class ST> struct Nuts : NutsBase {
                 MM_HIP(hipGetDeviceProperties(&prop, device));
                 n_resident_waves = (unsigned int)prop.multiProcessorCount * 4u; /* one wave per SIMD */
                 MM_HIP(hipMalloc((void **)&d_lg_counts, (size_t)kMaxGroups * 2 * (MM_NUTS_JMAX + 1) * sizeof(unsigned int)));
-                variant = 3; /* the default where it exists */
             }
         }
-        if (!lg && k && k->run_async)
-            variant = 4; /* asynchronous lanes */
-        if (!lg && k && k->run_pair)
-            variant = 5; /* asynchronous lanes, leaves in pairs: the default for the one-chain-per-lane kernels */
+        caps.inst = k != nullptr;
+        caps.inst_async = k && k->run_async;
+        caps.inst_pair = k && k->run_pair;
+        caps.lg = lg != nullptr;
+        caps.generic_ok = generic_ok;
+        caps.unit = user != nullptr;
+        variant = mm_nuts_default_variant(caps);
         MM_HIP(hipStreamCreateWithFlags(&stream, hipStreamDefault));
         MM_HIP(hipEventCreate(&ev0));
         MM_HIP(hipEventCreate(&ev1));
         return MMCMC_OK;
     }
 
-    int set_variant(int v) override
+    /* one launch of the persistent scheduler; the kernel reports a stuck queue instead of hanging */
+    hipError_t launch_queue(const mm_nuts_lg_args &gq, const mm_nuts_lgq_shape &shape, hipStream_t st)
     {
-        if (met.kind != MM_METRIC_NONE || recording) /* only the metric unit has kernels that read a metric, only the stats unit kernels that record: it is variant 7 until the metric is cleared and recording is off */
-            return v == 7 ? MMCMC_OK : (v >= 0 && v <= 7) ? MMCMC_ERR_UNSUPPORTED : MMCMC_ERR_INVALID_ARG;
-        if ((v == 0 && k) || (v >= 1 && v <= 3 && lg) || (v == 4 && k && k->run_async) || (v == 5 && k && k->run_pair) ||
-            (v == 6 && generic_ok) || (v == 7 && user)) {
-            variant = v;
-            return MMCMC_OK;
-        }
-        return (v >= 0 && v <= 7) ? MMCMC_ERR_UNSUPPORTED : MMCMC_ERR_INVALID_ARG;
+        ++n_launches_run;
+        hipError_t e = lg->run_queue(gq, shape.nw, shape.occ, st);
+        if (e != hipSuccess)
+            return e;
+        mm_lgq_ctrl hc;
+        if ((e = hipMemcpyAsync(&hc, d_lg_ctrl, sizeof(hc), hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return e;
+        if ((e = hipStreamSynchronize(st)) != hipSuccess)
+            return e;
+        if (mm_tuning_env("MMCMC_LGQ_STATS"))
+            fprintf(stderr, "lgq: first level %d units %llu chains %llu (%.2f per unit) leaf iterations %llu idle polls %llu error %u ticks pick %.3g fetch %.3g work %.3g handover %.3g\n",
+                    gq.j0, hc.stat_units, hc.stat_chains, (double)hc.stat_chains / (double)(hc.stat_units ? hc.stat_units : 1),
+                    hc.stat_leaf_iters, hc.stat_polls, (unsigned int)hc.error, (double)hc.stat_t[0], (double)hc.stat_t[1],
+                    (double)hc.stat_t[2], (double)hc.stat_t[3]);
+        return (hc.error != 0ull || hc.remaining != 0ull) ? hipErrorLaunchFailure : hipSuccess;
     }
-
+    /* the first compaction level from the handle's depth histogram (mm_nuts_level_from_hist), kept in auto_level once known */
+    hipError_t read_level(hipStream_t st)
+    {
+        unsigned int hh[MM_NUTS_JMAX + 1];
+        hipError_t e = hipMemcpyAsync(hh, d_hist, sizeof(hh), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
+            return e;
+        const int level = mm_nuts_level_from_hist(hh, n_chains, max_depth);
+        if (level >= 0)
+            auto_level = level;
+        return hipSuccess;
+    }
+    /* variant 3, the persistent scheduler: one launch, or (a fresh handle, mm_nuts_pilot_split) a pilot and the rest */
+    hipError_t run_lg_queue(mm_nuts_lg_args g, hipStream_t st)
+    {
+        g.ctrl = d_lg_ctrl;
+        g.slots = d_lg_lists;
+        const mm_nuts_lgq_shape shape =
+            mm_nuts_lgq_grid((unsigned int)(c_pad / 16), n_resident_waves, lgq_occ, knob("MMCMC_LGQ_OCC"), knob("MMCMC_LGQ_WAVES"));
+        if (!compaction_auto) /* the caller fixed the level */
+            return launch_queue(g, shape, st);
+        /* once the histogram has fixed the level it is kept: no device-to-host copy and no stream synchronisation per run()
+         * after that */
+        hipError_t e = auto_level < 0 ? read_level(st) : hipSuccess;
+        if (e != hipSuccess)
+            return e;
+        const mm_knob pilot = knob("MMCMC_LGQ_PILOT"), pilot_level = knob("MMCMC_LGQ_PILOT_LEVEL");
+        const mm_nuts_pilot_plan plan = mm_nuts_pilot_split({g.m0, g.n_pre, g.n_rec, g.write_initial, g.out_t0}, auto_level >= 0,
+                                                            pilot.set ? (unsigned int)pilot.value : mm_nuts_lgq_pilot);
+        for (int i = 0; i < plan.n; ++i) {
+            const bool is_pilot = plan.n == 2 && i == 0; /* runs at the default level, then the histogram is read */
+            const mm_nuts_segment &s = plan.seg[i];
+            mm_nuts_lg_args q = g;
+            q.m0 = s.m0;
+            q.n_pre = s.n_pre;
+            q.n_rec = s.n_rec;
+            q.write_initial = s.write_initial;
+            q.out_t0 = s.out_t0;
+            if (is_pilot && pilot_level.set)
+                q.j0 = pilot_level.value;
+            if (!is_pilot && auto_level >= 0)
+                q.j0 = auto_level < max_depth ? auto_level : max_depth;
+            if ((e = launch_queue(q, shape, st)) != hipSuccess || (is_pilot && (e = read_level(st)) != hipSuccess))
+                return e;
+        }
+        return hipSuccess;
+    }
+    /* variant 2, one launch per level and transition: the chain groups of mm_nuts_lg_group_of, each with its own launch
+     * sequence on its own stream between a fork and a join on `st` */
+    hipError_t run_lg_levels(const mm_nuts_lg_args &g, hipStream_t st)
+    {
+        const int n_groups = mm_nuts_lg_n_groups(compaction_groups, n_chains, c_pad);
+        const mm_nuts_segment run = {g.m0, g.n_pre, g.n_rec, g.write_initial, g.out_t0};
+        hipError_t e = hipMemsetAsync(d_lg_counts, 0, (size_t)kMaxGroups * 2 * (MM_NUTS_JMAX + 1) * sizeof(unsigned int), st);
+        if (e != hipSuccess)
+            return e;
+        if (!lg_fork && (e = hipEventCreateWithFlags(&lg_fork, hipEventDisableTiming)) != hipSuccess)
+            return e;
+        if ((e = hipEventRecord(lg_fork, st)) != hipSuccess)
+            return e;
+        for (int gi = 0; gi < n_groups; ++gi) {
+            if (!lg_streams[gi] && (e = hipStreamCreateWithFlags(&lg_streams[gi], hipStreamNonBlocking)) != hipSuccess)
+                return e;
+            if (!lg_join[gi] && (e = hipEventCreateWithFlags(&lg_join[gi], hipEventDisableTiming)) != hipSuccess)
+                return e;
+            const mm_nuts_lg_group grp = mm_nuts_lg_group_of(gi, n_groups, n_chains, c_pad);
+            const size_t off = grp.offset;
+            mm_nuts_lg_args q = g;
+            q.n_chains = grp.n_chains;
+            q.c_pad = grp.c_pad;
+            q.chain_offset = g.chain_offset + off;
+            q.state = g.state + off * (size_t)dim;
+            q.adapt = g.adapt + off;
+            q.out = g.out ? g.out + off * g.n_total * (size_t)dim : nullptr;
+            q.n_leapfrog = g.n_leapfrog ? g.n_leapfrog + off : nullptr;
+            q.scratch = d_lg_scratch + grp.w0 * lg->scratch_doubles_per_wave;
+            q.rec = d_lg_rec + off * lg->rec_doubles_per_chain;
+            q.lists = d_lg_lists + (size_t)MM_NUTS_JMAX * off;
+            q.counts = d_lg_counts + (size_t)gi * 2 * (MM_NUTS_JMAX + 1);
+            hipStream_t gs = lg_streams[gi];
+            if ((e = hipStreamWaitEvent(gs, lg_fork, 0)) != hipSuccess)
+                return e;
+            for (unsigned int t = 0; t < run.n_pre + run.n_rec && e == hipSuccess; ++t) {
+                const mm_nuts_lg_step s = mm_nuts_lg_step_of(run, t);
+                q.m = s.m;
+                q.write_initial = s.write_initial;
+                q.row = s.row;
+                e = lg->run_transition(q, gs);
+            }
+            if (e != hipSuccess)
+                return e;
+            if ((e = hipEventRecord(lg_join[gi], gs)) != hipSuccess)
+                return e;
+            if ((e = hipStreamWaitEvent(st, lg_join[gi], 0)) != hipSuccess)
+                return e;
+        }
+        return hipSuccess;
+    }
     /* the lane-group launch exists for <double, double> only; the other instantiations never reach it */
     hipError_t run_lg(const mm_nuts_args<TT, ST> &a, hipStream_t st)
     {
         if constexpr (std::is_same<TT, double>::value && std::is_same<ST, double>::value) {
-            mm_nuts_lg_args g;
+            mm_nuts_lg_args g = shared_nuts_args<mm_nuts_lg_args>(a);
             g.mat = d_mat;
-            g.state = a.state;
-            g.adapt = a.adapt;
-            g.out = a.out;
-            g.n_leapfrog = a.n_leapfrog;
-            g.depth_hist = a.depth_hist;
-            g.n_chains = a.n_chains;
-            g.seed = a.seed;
-            g.chain_offset = a.chain_offset;
-            g.n_total = a.n_total;
-            g.m0 = a.m0;
-            g.n_pre = a.n_pre;
-            g.n_rec = a.n_rec;
-            g.write_initial = a.write_initial;
-            g.out_t0 = a.out_t0;
-            g.n_discard = a.n_discard;
-            g.max_depth = a.max_depth;
-            g.target_accept_p = a.target_accept_p;
             g.scratch = d_lg_scratch;
             g.rec = d_lg_rec;
             g.c_pad = c_pad;
@@ -649,174 +804,17 @@ template <class TT, class ST> struct Nuts : NutsBase {
             g.row = 0xffffffffu;
             g.ctrl = nullptr;
             g.slots = nullptr;
-            const unsigned int total = a.n_pre + a.n_rec;
-            /* few chains cannot fill the queues of a scheduler: one launch, every wave keeps its chains */
-            if (variant == 1 || total == 0 || (variant == 3 && n_chains < 2048))
+            const mm_knob patience = knob("MMCMC_LGQ_PATIENCE"), min_unit = knob("MMCMC_LGQ_MIN_UNIT");
+            g.patience = patience.set ? (unsigned int)patience.value : mm_nuts_lgq_patience;
+            g.min_unit = min_unit.set ? (unsigned int)min_unit.value : mm_nuts_lgq_min_unit;
+            switch (mm_nuts_lg_mode(variant, a.n_pre + a.n_rec, n_chains, c_pad)) {
+            case MM_NLG_SINGLE:
                 return lg->run(g, st);
-            if (variant == 3 && c_pad < (1ull << MM_LGQ_ID_BITS)) {
-                /* persistent scheduler: one resident wave per SIMD (fewer if there are fewer groups of 16 chains) */
-                g.ctrl = d_lg_ctrl;
-                g.slots = d_lg_lists;
-                /* idle polls before a wave settles for less than a full unit.  Round 2 (65 536 chains): 4 -> 516.5 ms, 16 -> 518.5,
-                 * 64 -> 520.9, 256 -> 530.3; round 6, with the leaf loop 25 % faster: 0 / 1 / 2 / 4 / 8 -> 347.9 / 348.0 / 348.5 /
-                 * 349.3 / 349.7 ms at 15.75-15.77 chains per unit (profiles/r6zh_lgq_patience.log): waiting buys no fuller units */
-                g.patience = 1u;
-                if (const char *ev = mm_tuning_env("MMCMC_LGQ_PATIENCE"))
-                    g.patience = (unsigned int)atoi(ev);
-                /* a wave stays with the chains it kept only when the queue of their level makes a FULL unit of them; else they
-                 * are queued and the wave takes the deepest full unit there is (config 5 with the edges in registers: 10 ->
-                 * 408.6 ms, 12 -> 390.1, 14 -> 381.2, 16 -> 377.5: 15.27 -> 15.78 chains per unit;
-                 * profiles/r5zzz_lgq_min_unit.log) */
-                g.min_unit = 16u;
-                if (const char *ev = mm_tuning_env("MMCMC_LGQ_MIN_UNIT"))
-                    g.min_unit = (unsigned int)atoi(ev);
-                const unsigned int groups16 = (unsigned int)(c_pad / 16);
-                /* waves per SIMD the scheduler is built for (mm_lg_cfg): 2 wherever two per SIMD can be filled */
-                int occ = lgq_occ;
-                if (const char *ev = mm_tuning_env("MMCMC_LGQ_OCC"))
-                    occ = atoi(ev) == 2 ? 2 : 1;
-                if (groups16 < 2u * n_resident_waves)
-                    occ = 1;
-                const unsigned int resident = n_resident_waves * (unsigned int)occ;
-                unsigned int nw = groups16 < resident ? groups16 : resident;
-                if (const char *ev = mm_tuning_env("MMCMC_LGQ_WAVES")) {
-                    const unsigned int w = (unsigned int)atoi(ev);
-                    if (w >= 1 && w < nw)
-                        nw = w;
-                }
-                /* one launch of the scheduler; the kernel reports a stuck queue instead of hanging */
-                auto launch = [&](const mm_nuts_lg_args &gq) -> hipError_t {
-                    ++n_launches_run;
-                    hipError_t e = lg->run_queue(gq, nw, occ, st);
-                    if (e != hipSuccess)
-                        return e;
-                    mm_lgq_ctrl hc;
-                    if ((e = hipMemcpyAsync(&hc, d_lg_ctrl, sizeof(hc), hipMemcpyDeviceToHost, st)) != hipSuccess)
-                        return e;
-                    if ((e = hipStreamSynchronize(st)) != hipSuccess)
-                        return e;
-                    if (mm_tuning_env("MMCMC_LGQ_STATS"))
-                        fprintf(stderr, "lgq: first level %d units %llu chains %llu (%.2f per unit) leaf iterations %llu idle polls %llu error %u ticks pick %.3g fetch %.3g work %.3g handover %.3g\n",
-                                gq.j0, hc.stat_units, hc.stat_chains,
-                                (double)hc.stat_chains / (double)(hc.stat_units ? hc.stat_units : 1), hc.stat_leaf_iters,
-                                hc.stat_polls, (unsigned int)hc.error, (double)hc.stat_t[0], (double)hc.stat_t[1],
-                                (double)hc.stat_t[2], (double)hc.stat_t[3]);
-                    return (hc.error != 0ull || hc.remaining != 0ull) ? hipErrorLaunchFailure : hipSuccess;
-                };
-                /* The first compaction level pays when it sits just below the depth most trees reach (config 5, trees
-                 * 7 - 8 deep: level 5 660 ms, 7 648 ms, 8 782 ms at 65 536 chains; 234 -> 203 ms at 16 384).  Unless the
-                 * caller fixed it, it is the mode of the handle's depth histogram minus one; a fresh handle runs its
-                 * first 16 transitions as a pilot with the default to have a histogram.  Splitting a run never changes a
-                 * result (the stream is keyed by chain and step). */
-                auto level_from_history = [&](int *level) -> hipError_t {
-                    unsigned int hh[MM_NUTS_JMAX + 1];
-                    hipError_t e = hipMemcpyAsync(hh, d_hist, sizeof(hh), hipMemcpyDeviceToHost, st);
-                    if (e != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
-                        return e;
-                    unsigned long long sum = 0;
-                    int mode = 0;
-                    for (int i = 0; i <= MM_NUTS_JMAX; ++i) {
-                        sum += hh[i];
-                        if (hh[i] > hh[mode])
-                            mode = i;
-                    }
-                    if (sum >= 8ull * n_chains) {
-                        int l = mode - 1;
-                        l = l < 3 ? 3 : l;
-                        *level = l < max_depth ? l : max_depth;
-                    }
-                    return hipSuccess;
-                };
-                if (compaction_auto) {
-                    /* once the histogram has fixed the level it is kept: no device-to-host copy and no stream
-                     * synchronisation per run() after that */
-                    int level = auto_level;
-                    hipError_t e = level < 0 ? level_from_history(&level) : hipSuccess;
-                    if (e != hipSuccess)
-                        return e;
-                    if (level >= 0)
-                        auto_level = level;
-                    unsigned int pilot = 16;
-                    if (const char *ev = mm_tuning_env("MMCMC_LGQ_PILOT"))
-                        pilot = (unsigned int)atoi(ev);
-                    if (level < 0 && total >= 4 * pilot) {
-                        mm_nuts_lg_args g1 = g, g2 = g;
-                        if (const char *ev = mm_tuning_env("MMCMC_LGQ_PILOT_LEVEL"))
-                            g1.j0 = atoi(ev);
-                        g1.n_pre = a.n_pre < pilot ? a.n_pre : pilot;
-                        g1.n_rec = pilot - g1.n_pre;
-                        if ((e = launch(g1)) != hipSuccess)
-                            return e;
-                        if ((e = level_from_history(&level)) != hipSuccess)
-                            return e;
-                        if (level >= 0)
-                            auto_level = level;
-                        g2.m0 = a.m0 + pilot;
-                        g2.n_pre = a.n_pre - g1.n_pre;
-                        g2.n_rec = a.n_rec - g1.n_rec;
-                        g2.write_initial = 0;
-                        g2.out_t0 = a.out_t0 + (a.write_initial ? 1u : 0u) + g1.n_rec;
-                        if (level >= 0)
-                            g2.j0 = level < max_depth ? level : max_depth;
-                        return launch(g2);
-                    }
-                    if (level >= 0)
-                        g.j0 = level < max_depth ? level : max_depth;
-                }
-                return launch(g);
+            case MM_NLG_QUEUE:
+                return run_lg_queue(g, st);
+            default:
+                return run_lg_levels(g, st);
             }
-            /* Tree-depth compaction: 1 + (max_depth - j0) launches per transition.  The late launches of a
-             * transition hold few chains (a few per cent reach the deepest level), so the chains are split into
-             * groups, each with its own launch sequence on its own stream: one group's narrow launches run beside
-             * another's wide ones.  Groups are contiguous blocks of chains (a multiple of 16 each). */
-            int n_groups = compaction_groups > 0 ? compaction_groups : (int)(n_chains / 16384);
-            n_groups = n_groups < 1 ? 1 : (n_groups > kMaxGroups ? kMaxGroups : n_groups);
-            const size_t waves = c_pad / 16;
-            if ((size_t)n_groups > waves)
-                n_groups = (int)waves;
-            hipError_t e = hipMemsetAsync(d_lg_counts, 0, (size_t)kMaxGroups * 2 * (MM_NUTS_JMAX + 1) * sizeof(unsigned int), st);
-            if (e != hipSuccess)
-                return e;
-            if (!lg_fork && (e = hipEventCreateWithFlags(&lg_fork, hipEventDisableTiming)) != hipSuccess)
-                return e;
-            if ((e = hipEventRecord(lg_fork, st)) != hipSuccess)
-                return e;
-            for (int gi = 0; gi < n_groups; ++gi) {
-                if (!lg_streams[gi] && (e = hipStreamCreateWithFlags(&lg_streams[gi], hipStreamNonBlocking)) != hipSuccess)
-                    return e;
-                if (!lg_join[gi] && (e = hipEventCreateWithFlags(&lg_join[gi], hipEventDisableTiming)) != hipSuccess)
-                    return e;
-                const size_t w0 = waves * gi / n_groups, w1 = waves * (gi + 1) / n_groups;
-                const size_t off = w0 * 16;
-                mm_nuts_lg_args q = g;
-                q.n_chains = (w1 * 16 < a.n_chains ? w1 * 16 : a.n_chains) - off;
-                q.c_pad = (w1 - w0) * 16;
-                q.chain_offset = a.chain_offset + off;
-                q.state = a.state + off * (size_t)dim;
-                q.adapt = a.adapt + off;
-                q.out = a.out ? a.out + off * a.n_total * (size_t)dim : nullptr;
-                q.n_leapfrog = a.n_leapfrog ? a.n_leapfrog + off : nullptr;
-                q.scratch = d_lg_scratch + w0 * lg->scratch_doubles_per_wave;
-                q.rec = d_lg_rec + off * lg->rec_doubles_per_chain;
-                q.lists = d_lg_lists + (size_t)MM_NUTS_JMAX * off;
-                q.counts = d_lg_counts + (size_t)gi * 2 * (MM_NUTS_JMAX + 1);
-                hipStream_t gs = lg_streams[gi];
-                if ((e = hipStreamWaitEvent(gs, lg_fork, 0)) != hipSuccess)
-                    return e;
-                for (unsigned int t = 0; t < total && e == hipSuccess; ++t) {
-                    q.m = a.m0 + t + 1;
-                    q.write_initial = (t == 0) ? a.write_initial : 0u;
-                    q.row = (t >= a.n_pre) ? (a.out_t0 + (a.write_initial ? 1u : 0u) + (t - a.n_pre)) : 0xffffffffu;
-                    e = lg->run_transition(q, gs);
-                }
-                if (e != hipSuccess)
-                    return e;
-                if ((e = hipEventRecord(lg_join[gi], gs)) != hipSuccess)
-                    return e;
-                if ((e = hipStreamWaitEvent(st, lg_join[gi], 0)) != hipSuccess)
-                    return e;
-            }
-            return hipSuccess;
         } else {
             (void)a;
             (void)st;
@@ -831,26 +829,77 @@ template <class TT, class ST> struct Nuts : NutsBase {
             return hipErrorInvalidValue;
     }
 
-    /* one launch of the pair kernel (compiled instance or run-time compiled unit) */
-    hipError_t launch_pair(const mm_nuts_args<TT, ST> &a, bool rtc_target, int type_mode, hipStream_t st)
+    /* the run of a run-time compiled target: asynchronous lanes with the leaves in pairs (mm_nuts_pair_body; dynamic LDS = the
+     * ring of uniforms, stack in the scratch area).  The unit's lanes-in-step kernel (mm_nuts_run_body) is NOT launched: it gave
+     * wrong, run-to-run different samples at RosenbrockND(19) / (23) in f64 and a memory fault at StandardNormal(25) in f32,
+     * while the same template compiled into the library by hipcc is correct at those dimensions
+     * (tools/experiments/repro_nuts_dims.py).  Round 6 (mm_rtc.hip, at g_compiler): it was the hipRTC the process had loaded --
+     * PyTorch's bundled one, whose comgr is the 7.0.2 compiler; the system's 7.2 hipRTC emits hipcc's code and is correct, and
+     * today's sources compile correctly under both.  The policy stays: the pair kernel passed every comparison under every
+     * compiler, and every unit is checked against a second kernel before its first use (rtc_unit_verified) */
+    hipError_t run_target_unit(mm_nuts_args<TT, ST> a, hipStream_t st)
     {
-        if (rtc_target) {
-            mm_nuts_args<TT, ST> b = a;
-            const unsigned int grid = (unsigned int)((b.n_chains + 63) / 64);
-            return mm_rtc_launch_nuts(user, type_mode, 2, &b, sizeof(b), grid, (size_t)MM_NUTS_RING * 64 * sizeof(double), st);
+        int run_kernel = rtc_run_kernel;
+        /* measurement builds: launch the unit's lanes-in-step kernel from an ordinary handle (never inside the unit's check)
+         * -- tools/experiments/rtc_lanes_in_step.py asks whether hipRTC still gets that kernel wrong */
+        const mm_knob rk = knob("MMCMC_RTC_RUN_KERNEL");
+        if (rk.set && g_rtc_create_mode == 0)
+            run_kernel = rk.value == 0 ? 0 : 2;
+        const unsigned int grid64 = (unsigned int)((n_chains + 63) / 64);
+        return run_kernel == 2 ? mm_rtc_launch_nuts(user, type_mode, 2, &a, sizeof(a), grid64, (size_t)MM_NUTS_RING * 64 * sizeof(double), st)
+                               : mm_rtc_launch_nuts(user, type_mode, 0, &a, sizeof(a), grid64, user_lds, st); /* dynamic LDS = its output tile */
+    }
+    /* the run-time-dimension kernels' block: the run's, the store (mm_gen_nuts_vectors(max_depth) vectors of dim elements per
+     * chain, lane-interleaved; run() has sized it) */
+    mm_gen_nuts_args<TT, ST> generic_args(const mm_nuts_args<TT, ST> &a) const
+    {
+        auto ga = shared_nuts_args<mm_gen_nuts_args<TT, ST>>(a);
+        ga.P = P;
+        ga.kind = kind;
+        ga.dim = dim;
+        ga.store = d_gstore;
+        ga.c_pad = g_pad;
+        ga.eps_tol = eps_tol;
+        return ga;
+    }
+    /* the unit of a handle with a metric or one that records: the stats unit of the metric kind while recording */
+    const mm_user_target *own_unit(mm_nuts_launch path) const
+    {
+        return path == MM_NLAUNCH_METRIC_UNIT ? metric_unit : path == MM_NLAUNCH_DENSE_UNIT ? dense_unit : stats_unit[path - MM_NLAUNCH_STATS_UNIT];
+    }
+    /* one launch on the handle's path: init_chain (nuts.rs:528-545, on every run() call) or the run itself */
+    hipError_t launch(mm_nuts_launch path, bool init, mm_nuts_init_args<TT, ST> ia, const mm_nuts_args<TT, ST> &a, hipStream_t st)
+    {
+        switch (path) {
+        case MM_NLAUNCH_INST_STEP:
+        case MM_NLAUNCH_INST_ASYNC:
+        case MM_NLAUNCH_INST_PAIR:
+            if (init)
+                return k->init(P, d_state, d_adapt, n_chains, seed, chain_offset, st);
+            return path == MM_NLAUNCH_INST_PAIR ? k->run_pair(a, st) : path == MM_NLAUNCH_INST_ASYNC ? k->run_async(a, st) : k->run(a, st);
+        case MM_NLAUNCH_LG:
+            return init ? init_lg(st) : run_lg(a, st);
+        case MM_NLAUNCH_GENERIC:
+            return launch_generic(generic_args(a), init ? 1 : 0, st);
+        case MM_NLAUNCH_TARGET_UNIT:
+            return init ? mm_rtc_launch_nuts(user, type_mode, 1, &ia, sizeof(ia), (unsigned int)((n_chains + 63) / 64), 0, st) : run_target_unit(a, st);
+        case MM_NLAUNCH_NONE:
+            return hipErrorInvalidValue;
+        default: /* the metric unit's or the stats unit's pair kernel, its stack in the handle's metric scratch area */
+            return init ? unit_init(own_unit(path), met.kind, ia, d_metric, st)
+                        : unit_run(own_unit(path), met.kind, a, 2, d_metric, recording, a.n_total ? d_rec : nullptr, st);
         }
-        return k->run_pair(a, st);
     }
 
     int run(size_t n_collect, size_t n_discard, void *out, int out_is_device, int progress, void *stream_v) override
     {
-        if (progress < 0 || progress > 2)
-            return MMCMC_ERR_INVALID_ARG;
-        /* progress == 2: run_progress' stepping with EVERY state recorded, burn-in included (what the per-chain trackers of
-         * nuts.rs:486-506 are fed): out has n_collect + n_discard rows per chain */
-        const size_t n_rows = progress == 2 ? n_collect + n_discard : n_collect;
-        if ((uint64_t)n_rows * (uint64_t)dim >= (1ull << 30) || (uint64_t)m + n_collect + n_discard >= (1ull << 32))
-            return MMCMC_ERR_SHAPE;
+        const mm_nuts_steps steps = mm_nuts_step_plan(n_collect, n_discard, progress, dim, m);
+        if (steps.status != MMCMC_OK)
+            return steps.status;
+        const mm_nuts_launch path = mm_nuts_launch_path(caps, met.kind, recording, variant);
+        if (path == MM_NLAUNCH_NONE) /* no setter leaves a handle on a variant it lacks the kernels of */
+            return MMCMC_ERR_STATE;
+        const size_t n_rows = steps.n_rows;
         DevGuard g(device);
         hipStream_t st = stream_v ? (hipStream_t)stream_v : stream;
         const size_t out_bytes = n_chains * n_rows * (size_t)dim * sizeof(TT);
@@ -875,46 +924,12 @@ template <class TT, class ST> struct Nuts : NutsBase {
             }
         }
         n_launches_run = 0;
-        /* init_chain (nuts.rs:528-545) on every run() call */
-        const bool use_lg = variant >= 1 && variant <= 3 && lg;
-        const bool use_generic = variant == 6;
-        mm_gen_nuts_args<TT, ST> ga;
-        if (use_generic) {
-            /* the store: mm_gen_nuts_vectors(max_depth) vectors of dim elements per chain, lane-interleaved */
-            if (!d_gstore || gstore_depth < max_depth) {
-                (void)hipFree(d_gstore);
-                d_gstore = nullptr;
-                MM_HIP(hipMalloc((void **)&d_gstore, (size_t)mm_gen_nuts_vectors(max_depth) * (size_t)dim * g_pad * sizeof(TT)));
-                gstore_depth = max_depth;
-            }
-            ga.P = P;
-            ga.kind = kind;
-            ga.dim = dim;
-            ga.max_depth = max_depth;
-            ga.state = d_state;
-            ga.adapt = d_adapt;
-            ga.out = nullptr;
-            ga.n_leapfrog = d_nlf;
-            ga.depth_hist = d_hist;
-            ga.store = d_gstore;
-            ga.n_chains = n_chains;
-            ga.c_pad = g_pad;
-            ga.seed = seed;
-            ga.chain_offset = chain_offset;
-            ga.n_total = n_rows;
-            ga.m0 = m;
-            ga.n_pre = ga.n_rec = ga.write_initial = ga.out_t0 = 0;
-            ga.n_discard = (unsigned int)n_discard;
-            ga.target_accept_p = (ST)target_accept_p;
-            ga.eps_tol = sizeof(ST) == 4 ? (ST)1.1920929e-7 : (ST)2.220446049250313e-16; /* T::epsilon() */
+        if (path == MM_NLAUNCH_GENERIC && (!d_gstore || gstore_depth < max_depth)) {
+            (void)hipFree(d_gstore);
+            d_gstore = nullptr;
+            MM_HIP(hipMalloc((void **)&d_gstore, (size_t)mm_gen_nuts_vectors(max_depth) * (size_t)dim * g_pad * sizeof(TT)));
+            gstore_depth = max_depth;
         }
-        const int type_mode = std::is_same<TT, double>::value ? 2 : (std::is_same<ST, double>::value ? 0 : 1);
-        const unsigned int grid64 = (unsigned int)((n_chains + 63) / 64);
-        hipError_t e;
-        const bool has_metric = met.kind != MM_METRIC_NONE, has_dense = met.kind == MM_METRIC_DENSE;
-        const bool rtc_target = (user && variant == 7) || has_metric || recording; /* kernels of a run-time compiled unit */
-        /* the unit of a handle with a metric or one that records: the stats unit of the metric kind while recording */
-        const mm_user_target *const own_unit = recording ? stats_unit[met.kind] : has_dense ? dense_unit : metric_unit;
         if (recording) {
             const size_t need = n_chains * n_rows;
             if (need > rec_capacity) {
@@ -927,103 +942,19 @@ template <class TT, class ST> struct Nuts : NutsBase {
                 rec_capacity = need;
             }
         }
-        if (rtc_target) {
-            mm_nuts_init_args<TT, ST> ia;
-            ia.P = P;
-            ia.state = d_state;
-            ia.adapt = d_adapt;
-            ia.n_chains = n_chains;
-            ia.seed = seed;
-            ia.chain_offset = chain_offset;
-            ia.eps_tol = sizeof(ST) == 4 ? (ST)1.1920929e-7 : (ST)2.220446049250313e-16;
-            e = (has_metric || recording) ? unit_init(own_unit, met.kind, ia, d_metric, st) : mm_rtc_launch_nuts(user, type_mode, 1, &ia, sizeof(ia), grid64, 0, st);
-        } else {
-            e = use_lg ? init_lg(st) : use_generic ? launch_generic(ga, 1, st) : k->init(P, d_state, d_adapt, n_chains, seed, chain_offset, st);
-        }
+        /* a metric unit or a stats unit keeps its stack in the handle's metric scratch area */
+        const bool own = path >= MM_NLAUNCH_METRIC_UNIT;
+        mm_nuts_init_args<TT, ST> ia;
+        mm_nuts_args<TT, ST> a;
+        fill_args(Where{d_state, d_adapt, d_out, d_nlf, d_hist, own ? d_metric_scratch : d_scratch, n_chains, seed, chain_offset, m, max_depth,
+                        target_accept_p, !own && stack_in_lds},
+                  steps, n_discard, &ia, &a);
+        a.async_batch = (unsigned int)knob("MMCMC_NUTS_ASYNC_BATCH").value; /* tuning aid; no result depends on it */
+        hipError_t e = launch(path, true, ia, a, st);
         if (e != hipSuccess)
             return (int)e;
-        mm_nuts_args<TT, ST> a;
-        a.P = P;
-        a.state = d_state;
-        a.adapt = d_adapt;
-        a.out = d_out;
-        a.n_leapfrog = d_nlf;
-        a.depth_hist = d_hist;
-        a.n_chains = n_chains;
-        a.seed = seed;
-        a.chain_offset = chain_offset;
-        a.n_total = n_rows;
-        a.m0 = m;
-        a.out_t0 = 0;
-        a.n_discard = (unsigned int)n_discard;
-        a.max_depth = max_depth;
-        a.target_accept_p = (ST)target_accept_p;
-        a.stack_in_lds = stack_in_lds ? 1 : 0;
-        a.async_batch = 0;
-        if (const char *e = mm_tuning_env("MMCMC_NUTS_ASYNC_BATCH")) /* tuning aid; no result depends on it */
-            a.async_batch = (unsigned int)atoi(e);
-        a.scratch = d_scratch;
-        const size_t total = n_collect + n_discard;
-        if (progress == 2) {
-            a.write_initial = 0;
-            a.n_pre = 0;
-            a.n_rec = (unsigned int)total;
-        } else if (progress) {
-            /* run_progress (nuts.rs:491-522): all N transitions, the last n_collect recorded */
-            a.write_initial = 0;
-            a.n_pre = (unsigned int)n_discard;
-            a.n_rec = (unsigned int)n_collect;
-        } else if (total == 0) {
-            a.write_initial = 0;
-            a.n_pre = a.n_rec = 0;
-        } else if (n_discard == 0) {
-            /* run (nuts.rs:457-471): N - 1 transitions; row 0 is the initial point */
-            a.write_initial = n_collect > 0 ? 1 : 0;
-            a.n_pre = 0;
-            a.n_rec = (unsigned int)(n_collect > 0 ? n_collect - 1 : 0);
-        } else {
-            a.write_initial = 0;
-            a.n_pre = (unsigned int)(n_discard - 1);
-            a.n_rec = (unsigned int)n_collect;
-        }
         MM_HIP(hipEventRecord(ev0, st));
-        const unsigned int a_pre = a.n_pre, a_rec = a.n_rec;
-        if (has_metric || recording) {
-            /* the metric unit's or the stats unit's pair kernel, its stack in the handle's metric scratch area */
-            a.scratch = d_metric_scratch;
-            a.stack_in_lds = 0;
-            e = unit_run(own_unit, met.kind, a, 2, d_metric, recording, n_rows ? d_rec : nullptr, st);
-        } else if (rtc_target) {
-            /* a run-time compiled target: asynchronous lanes with the leaves in pairs (mm_nuts_pair_body; dynamic LDS = the
-             * ring of uniforms, stack in the scratch area).  The unit's lanes-in-step kernel (mm_nuts_run_body) is NOT
-             * launched: it gave wrong, run-to-run different samples at RosenbrockND(19) / (23) in f64 and a memory fault at
-             * StandardNormal(25) in f32, while the same template compiled into the library by hipcc is correct at those
-             * dimensions (tools/experiments/repro_nuts_dims.py).  Round 6 (mm_rtc.hip, at g_compiler): it was the hipRTC the
-             * process had loaded -- PyTorch's bundled one, whose comgr is the 7.0.2 compiler; the system's 7.2 hipRTC emits
-             * hipcc's code and is correct, and today's sources compile correctly under both.  The policy stays: the pair
-             * kernel passed every comparison under every compiler, and every unit is checked against a second kernel before
-             * its first use (rtc_unit_verified) */
-            int run_kernel = rtc_run_kernel;
-            /* measurement builds: launch the unit's lanes-in-step kernel from an ordinary handle (never inside the unit's
-             * check) -- tools/experiments/rtc_lanes_in_step.py asks whether hipRTC still gets that kernel wrong */
-            if (const char *rk = mm_tuning_env("MMCMC_RTC_RUN_KERNEL"))
-                if (g_rtc_create_mode == 0)
-                    run_kernel = atoi(rk) == 0 ? 0 : 2;
-            e = run_kernel == 2
-                    ? mm_rtc_launch_nuts(user, type_mode, 2, &a, sizeof(a), grid64, (size_t)MM_NUTS_RING * 64 * sizeof(double), st)
-                    : mm_rtc_launch_nuts(user, type_mode, 0, &a, sizeof(a), grid64, user_lds, st); /* dynamic LDS = its output tile */
-        } else if (use_generic) {
-            ga.out = d_out;
-            ga.n_pre = a.n_pre;
-            ga.n_rec = a.n_rec;
-            ga.write_initial = a.write_initial;
-            e = launch_generic(ga, 0, st);
-        } else {
-            e = use_lg ? run_lg(a, st)
-                       : (variant == 5 && k->run_pair) ? k->run_pair(a, st)
-                       : (variant == 4 && k->run_async) ? k->run_async(a, st) : k->run(a, st);
-        }
-        if (e != hipSuccess)
+        if ((e = launch(path, false, ia, a, st)) != hipSuccess)
             return (int)e;
         MM_HIP(hipEventRecord(ev1, st));
         if (recording) { /* the records of this run, one per row of its sample */
@@ -1031,11 +962,11 @@ template <class TT, class ST> struct Nuts : NutsBase {
             rec_first = 0;
             rec_valid = true;
         }
-        m += a_pre + a_rec;
+        m += steps.n_pre + steps.n_rec;
         timed = true;
-        /* sampling launches of this run (the persistent scheduler of a fresh handle: a 16-transition pilot plus the
-         * rest; compaction by launches: one per level and transition); kernel_ms is the time on the stream between the
-         * first and the last, host gaps of multi-launch runs included */
+        /* sampling launches of this run: the persistent scheduler counts its own (a fresh handle: a 16-transition pilot plus
+         * the rest); every other path reports 1, compaction by launches (one per level and transition) included; kernel_ms is
+         * the time on the stream between the first and the last, host gaps of multi-launch runs included */
         timing.n_launches = n_launches_run ? n_launches_run : 1;
         timing.out_bytes = d_out ? out_bytes : 0;
         timing.state_bytes = 2ull * n_chains * dim * sizeof(TT);

@@ -37,13 +37,27 @@ template <class TT, class ST> struct mm_nuts_args {
     unsigned char *scratch;    /* global stack storage when !stack_in_lds: per wave mm_nuts_stack_bytes<>() */
 };
 
+/* The pending-subtree stack of one wave (mm_nuts_stack: per lane MM_NUTS_JMAX entries of three D-vectors, one alpha and three
+ * counters) as functions of the element sizes and the dimension: the host sizes the stack area of a kernel whose dimension it
+ * learns at run time by the rule the layout below is defined through.  One region of `slots` values per lane, 16-byte aligned */
+constexpr size_t mm_nuts_stack_region(size_t slots, size_t esz) { return (slots * 64 * esz + 15) / 16 * 16; }
+constexpr size_t mm_nuts_stack_vec_bytes(size_t tsz, int D) { return mm_nuts_stack_region((size_t)MM_NUTS_JMAX * 3 * D, tsz); }
+constexpr size_t mm_nuts_stack_alpha_bytes(size_t ssz) { return mm_nuts_stack_region((size_t)MM_NUTS_JMAX, ssz); }
+constexpr size_t mm_nuts_stack_cnt_bytes() { return mm_nuts_stack_region((size_t)MM_NUTS_JMAX * 3, sizeof(uint32_t)); }
+constexpr size_t mm_nuts_stack_bytes(size_t tsz, size_t ssz, int D)
+{
+    return mm_nuts_stack_vec_bytes(tsz, D) + mm_nuts_stack_alpha_bytes(ssz) + mm_nuts_stack_cnt_bytes();
+}
+
 template <class TT, class ST, int D> struct mm_nuts_stack_layout {
     using S = mm_nuts_stack<TT, ST, D>;
+    static_assert(S::vec_slots == MM_NUTS_JMAX * 3 * D && S::alpha_slots == MM_NUTS_JMAX && S::cnt_slots == MM_NUTS_JMAX * 3,
+                  "the regions hold mm_nuts_stack's slots");
     /* per-wave bytes, regions 16-byte aligned: vec | alpha | cnt */
-    static constexpr size_t vec_bytes = ((size_t)S::vec_slots * 64 * sizeof(TT) + 15) / 16 * 16;
-    static constexpr size_t alpha_bytes = ((size_t)S::alpha_slots * 64 * sizeof(ST) + 15) / 16 * 16;
-    static constexpr size_t cnt_bytes = ((size_t)S::cnt_slots * 64 * sizeof(uint32_t) + 15) / 16 * 16;
-    static constexpr size_t bytes = vec_bytes + alpha_bytes + cnt_bytes;
+    static constexpr size_t vec_bytes = mm_nuts_stack_vec_bytes(sizeof(TT), D);
+    static constexpr size_t alpha_bytes = mm_nuts_stack_alpha_bytes(sizeof(ST));
+    static constexpr size_t cnt_bytes = mm_nuts_stack_cnt_bytes();
+    static constexpr size_t bytes = mm_nuts_stack_bytes(sizeof(TT), sizeof(ST), D);
     /* the same three regions for the first `levels` stack entries only (a run never uses more than max_depth) */
     __host__ __device__ static constexpr size_t bytes_for(int levels)
     {
