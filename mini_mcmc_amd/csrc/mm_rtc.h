@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "mm_rtc_units.h" /* the unit kinds, their kernel table and texts; MM_RTC_NUTS_PAIR_MAX_DIM */
+
 #define MM_USER_KIND_BASE 1000 /* = MMCMC_USER_KIND_BASE: kinds handed out by mmcmc_target_register_source */
 
 struct mm_user_target; /* opaque */
@@ -18,7 +20,8 @@ int mm_rtc_is_model(const mm_user_target *t);
 size_t mm_rtc_data_len(const mm_user_target *t);
 /* an integer-state model (mmcmc_discrete_register_source); `args` = mm_discrete_user_args, one wave per workgroup */
 int mm_rtc_is_discrete(const mm_user_target *t);
-/* a unit the library built for itself (mm_rtc_builtin / mm_rtc_builtin_nuts): not a kind a caller may pass in a description */
+/* a unit the library built for itself (mm_rtc_builtin / mm_rtc_builtin_nuts / mm_rtc_metric_unit / mm_rtc_stats_unit): not a kind
+ * a caller may pass in a description */
 int mm_rtc_is_internal(const mm_user_target *t);
 /* MMCMC_RTC_COMPILER_HIPCC / _HIPRTC: which compiler built the unit */
 int mm_rtc_compiler(const mm_user_target *t);
@@ -48,10 +51,11 @@ hipError_t mm_rtc_launch_run(const mm_user_target *t, int sampler, int dtype, vo
 /* NUTS kernels of a registered target: mode 0 / 1 / 2 (mm_nuts_api.hip), init = 1: init_chain (`args` = mm_nuts_init_args<TT, ST>),
  * 0: the run with the lanes in step (`args` = mm_nuts_args<TT, ST>, stack in the HBM scratch area), 2: the run with asynchronous
  * lanes and leaves in pairs (mm_nuts_pair_body; dynamic LDS = the ring of uniforms; hipErrorNotFound if the unit lacks it: it is
- * compiled up to MM_RTC_NUTS_PAIR_MAX_DIM; the caller decides by the size of a chain's vectors); one wave per workgroup */
-#define MM_RTC_NUTS_PAIR_MAX_DIM 32
-/* init_chain and the asynchronous-lane pair kernel of `mode` exist on the current device (the only NUTS run kernel of a
- * run-time compiled unit that is launched: mm_nuts_api.hip) */
+ * compiled up to MM_RTC_NUTS_PAIR_MAX_DIM (mm_rtc_units.h); the caller decides by the size of a chain's vectors); one wave per
+ * workgroup */
+/* init_chain and the asynchronous-lane pair kernel of `mode` exist on the current device: what a handle needs before it takes
+ * a run-time compiled unit.  Its run() launches either run kernel (mm_nuts_api.hip: the pair kernel, init 2, or the
+ * lanes-in-step kernel, init 0, as the handle's kernel path says) */
 int mm_rtc_nuts_usable(const mm_user_target *t, int mode);
 hipError_t mm_rtc_launch_nuts(const mm_user_target *t, int mode, int init, void *args, size_t args_bytes, unsigned int grid, size_t lds,
                               hipStream_t stream);
