@@ -9,10 +9,15 @@
  * own slice of every chunk, so the destination's page faults and the DRAM traffic are spread over cores).  A destination
  * that IS pinned (hipHostMalloc / hipHostRegister / torch's pin_memory) gets the one direct copy as before.
  *
- * One stager per device (its own buffers and lock: shards of a device group copy side by side over their own links; they
- * share the copy-thread budget, and waiting threads yield the CPU after a short spin).  The 32 MB pinned ring of a device
- * that has staged once stays with the process (freeing pinned memory from a static destructor races the runtime's own
- * teardown); hosts with a single usable CPU get the plain copy.
+ * One stager per device (its own buffers and lock: shards of a device group copy side by side over their own links).  A
+ * copy that enters while others are in flight takes fewer copy threads -- half the usable CPUs, at most 8, divided by the
+ * copies in flight when it enters -- and keeps them until it ends: eight shards entering together hold 8 + 4 + 2 + 2 + 1 + 1 +
+ * 1 + 1 = 20 copy threads and 8 drivers, not 8 x (8 + 1), but the sum is not capped (mm_hostcopy_threads); waiting threads
+ * yield the CPU after a short spin.  The 32 MB pinned ring of a device that has staged once stays with the process (freeing
+ * pinned memory from a static destructor races the runtime's own teardown); hosts with a single usable CPU get the plain copy.
+ *
+ * The thresholds, the chunk and slice arithmetic and the ring's ordering protocol are mm_hostcopy_plan.h, host-only and run
+ * under the thread sanitizer by tests/cpp/hostcopy_ring.cpp; here: the stager, the pinned-destination test and HIP's transport.
  */
 #include "mm_hostcopy.h"
 
@@ -20,16 +25,14 @@
 #include <unistd.h>
 
 #include <atomic>
-#include <cstring>
 #include <mutex>
-#include <thread>
-#include <vector>
+
+#include "mm_hostcopy_plan.h"
 
 namespace {
 
-constexpr size_t kChunk = 8u << 20; /* 0.15 ms of DMA per chunk: the ring's latency; 4 chunks in flight */
-constexpr int kRing = 4;
-constexpr size_t kDirectBelow = 4u << 20; /* small results: the plain copy (its staging inside the runtime is as good) */
+constexpr size_t kChunk = kHostcopyChunk;
+constexpr int kRing = kHostcopyRing;
 
 struct Stager {
     std::mutex mu;
@@ -55,18 +58,9 @@ int usable_cpus()
     return n < 1 ? 1 : n;
 }
 
-/* staged copies in flight in this process (the shards of a device group copy side by side): they SHARE the copy-thread
- * budget -- eight shards no longer start 8 x (8 + 1) spinning threads on a 16-CPU affinity mask */
+/* staged copies in flight in this process (the shards of a device group copy side by side): a copy that enters beside others
+ * takes fewer copy threads (mm_hostcopy_threads) */
 std::atomic<int> g_active{0};
-
-int copy_threads(int cpus, int active)
-{
-    /* DRAM, not cores, is the limit from a handful of threads on; leave half the usable CPUs to the caller */
-    int n = cpus / 2;
-    n = n < 1 ? 1 : (n > 8 ? 8 : n);
-    n = n / (active < 1 ? 1 : active);
-    return n < 1 ? 1 : n;
-}
 
 bool is_pinned_host(const void *p)
 {
@@ -78,26 +72,31 @@ bool is_pinned_host(const void *p)
     return a.type == hipMemoryTypeHost;
 }
 
-/* waiting: `pause` for the first few hundred polls (a chunk is 0.15 ms of DMA), then give the CPU away between polls */
-struct Backoff {
-    unsigned int spins = 0;
-    void wait()
-    {
-        if (++spins < 256) {
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        } else {
-            sched_yield();
-        }
-    }
-    void reset() { spins = 0; }
-};
-
 struct ActiveGuard {
     int n;
     ActiveGuard() : n(g_active.fetch_add(1, std::memory_order_relaxed) + 1) {}
     ~ActiveGuard() { g_active.fetch_sub(1, std::memory_order_relaxed); }
+};
+
+/* the ring's transport: the DMA engine fills slot s on `stream`, an event per slot says when */
+struct HipTransport {
+    Stager &st;
+    const void *d_src;
+    hipStream_t stream;
+    const void *slot(int s) const { return st.pin[s]; }
+    int issue(int s, size_t off, size_t len)
+    {
+        hipError_t e;
+        if ((e = hipMemcpyAsync(st.pin[s], (const char *)d_src + off, len, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+            (e = hipEventRecord(st.ev[s], stream)) != hipSuccess)
+            return (int)e;
+        return 0;
+    }
+    int query(int s)
+    {
+        const hipError_t q = hipEventQuery(st.ev[s]);
+        return q == hipSuccess ? 0 : q == hipErrorNotReady ? kHostcopyNotReady : (int)q;
+    }
 };
 
 } // namespace
@@ -108,8 +107,8 @@ hipError_t mm_copy_to_host(void *dst, const void *d_src, size_t bytes, int devic
         return hipSuccess;
     hipError_t e;
     const int cpus = usable_cpus();
-    /* with one usable CPU a copy thread and the DMA driver would only take turns: the plain copy */
-    if (bytes < kDirectBelow || cpus < 2 || is_pinned_host(dst)) {
+    /* the runtime is asked about the destination only where its answer decides */
+    if (mm_hostcopy_direct(bytes, cpus, false) || mm_hostcopy_direct(bytes, cpus, is_pinned_host(dst))) {
         if ((e = hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, stream)) != hipSuccess)
             return e;
         return hipStreamSynchronize(stream);
@@ -126,88 +125,18 @@ hipError_t mm_copy_to_host(void *dst, const void *d_src, size_t bytes, int devic
         }
         st.ready = true;
     }
-    const size_t n_chunks = (bytes + kChunk - 1) / kChunk;
-    const int T = copy_threads(cpus, active.n);
-    /* published: chunks whose DMA has finished (the workers may read them); consumed[i % kRing]: workers done with chunk i */
-    std::atomic<size_t> published{0};
-    std::atomic<unsigned int> consumed[kRing];
-    std::atomic<bool> failed{false};
-    for (auto &c : consumed)
-        c.store(0, std::memory_order_relaxed);
-    auto worker = [&](int t) {
-        Backoff bo;
-        for (size_t i = 0; i < n_chunks; ++i) {
-            bo.reset();
-            while (published.load(std::memory_order_acquire) <= i) {
-                if (failed.load(std::memory_order_relaxed))
-                    return;
-                bo.wait();
-            }
-            const size_t off = i * kChunk, len = (off + kChunk <= bytes) ? kChunk : bytes - off;
-            /* slices on 4 KB boundaries: every destination page is faulted in and written by one thread */
-            const size_t per = ((len + (size_t)T - 1) / (size_t)T + 4095) & ~(size_t)4095;
-            const size_t a = (size_t)t * per, b = a + per < len ? a + per : len;
-            if (a < len)
-                std::memcpy((char *)dst + off + a, (const char *)st.pin[i % kRing] + a, b - a);
-            consumed[i % kRing].fetch_add(1, std::memory_order_release);
-        }
-    };
-    /* T copy threads beside this one, which drives the DMA ring.  A host that cannot start threads (resource limits) gets
-     * the plain copy: nothing may throw across the C ABI */
-    std::vector<std::thread> threads;
-    try {
-        threads.reserve((size_t)T);
-        for (int t = 0; t < T; ++t)
-            threads.emplace_back(worker, t);
-    } catch (...) {
-        failed.store(true, std::memory_order_relaxed);
-        for (std::thread &th : threads)
-            th.join();
+    /* T copy threads beside this one, which drives the DMA ring */
+    HipTransport tr{st, d_src, stream};
+    const mm_hostcopy_result r = mm_hostcopy_ring(tr, dst, bytes, kChunk, mm_hostcopy_threads(cpus, active.n));
+    if (!r.started) {
         if ((e = hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, stream)) != hipSuccess)
             return e;
         return hipStreamSynchronize(stream);
     }
-    size_t issued = 0, pub = 0;
-    e = hipSuccess;
-    Backoff bo;
-    while (pub < n_chunks) {
-        bool progressed = false;
-        if (issued < n_chunks) {
-            /* slot free: never used, or every worker is done with the chunk that used it */
-            const bool slot_free = issued < (size_t)kRing || consumed[issued % kRing].load(std::memory_order_acquire) >= (unsigned int)T;
-            if (slot_free) {
-                if (issued >= (size_t)kRing)
-                    consumed[issued % kRing].store(0, std::memory_order_relaxed);
-                const size_t off = issued * kChunk, len = (off + kChunk <= bytes) ? kChunk : bytes - off;
-                if ((e = hipMemcpyAsync(st.pin[issued % kRing], (const char *)d_src + off, len, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-                    (e = hipEventRecord(st.ev[issued % kRing], stream)) != hipSuccess)
-                    break;
-                ++issued;
-                progressed = true;
-            }
-        }
-        if (pub < issued) {
-            const hipError_t q = hipEventQuery(st.ev[pub % kRing]);
-            if (q == hipSuccess) {
-                published.store(++pub, std::memory_order_release);
-                progressed = true;
-            } else if (q != hipErrorNotReady) {
-                e = q;
-                break;
-            }
-        }
-        if (progressed)
-            bo.reset();
-        else
-            bo.wait();
-    }
+    e = (hipError_t)r.error;
     if (e != hipSuccess) {
-        failed.store(true, std::memory_order_relaxed);
         (void)hipGetLastError();
-    }
-    for (std::thread &th : threads)
-        th.join();
-    if (e != hipSuccess)
         (void)hipStreamSynchronize(stream); /* nothing of ours may still be in flight when the buffers are reused */
+    }
     return e;
 }
