@@ -57,19 +57,52 @@ MM_HD double mm_minT(double a, double b) { return fmin(a, b); }
  * itself -- the same bits as mm_minT(1, mm_exp_hotT(d)) for every d.  Written as a branch so that a wave none of whose
  * working lanes has d < 0 skips the exponential altogether (round 6: the tail of a one-chain-per-lane NUTS launch is ONE
  * live lane, half of whose leaves have d >= 0; in mode 0 the f64 exponential is ~30 two-slot instructions of its ~470 per leaf). */
-#ifndef MM_NUTS_ACCEPT_BRANCH
-#define MM_NUTS_ACCEPT_BRANCH 1
-#endif
 template <class ST> MM_HD ST mm_accept_stat(ST d)
 {
-#if MM_NUTS_ACCEPT_BRANCH
     ST a = ST(1);
     if (d < ST(0))
         a = mm_exp_hotT(d);
     return a;
-#else
-    return mm_minT(ST(1), mm_exp_hotT(d));
-#endif
+}
+
+/* ---- scalar rules stated once for every path: mm_nuts_tree below (hand_up and the pair walk), the run-time-dimension step
+ * (mm_nuts_generic.h) and the lane-group kernels (mm_nuts_lg.h) ---- */
+
+/* nuts.rs:908-915: the merged subtree keeps the SECOND child's proposal with probability n2 / max(n1 + n2, 1); u is always
+ * f64 (nuts.rs:910) */
+MM_HD bool mm_nuts_take2(double u, uint32_t n_first, uint32_t n_second)
+{
+    uint32_t den = n_first + n_second;
+    if (den < 1)
+        den = 1;
+    return u < ((double)n_second / (double)den);
+}
+
+/* dual averaging (nuts.rs:676-690) after transition m (1-based): alpha / n_alpha is the transition's acceptance statistic */
+template <class ST>
+MM_HD void mm_nuts_dual_average(mm_nuts_adapt<ST> &ad, uint32_t m, uint32_t n_discard, ST target_accept_p, ST alpha, uint32_t n_alpha)
+{
+    ST eta = ST(1) / (ST)(m + MM_NUTS_T0);
+    ad.h_bar = (ST(1) - eta) * ad.h_bar + eta * (target_accept_p - alpha / (ST)n_alpha);
+    if (m <= n_discard) {
+        const ST _m = (ST)m;
+        ad.epsilon = mm_expT(ad.mu - mm_sqrtT(_m) / ST(MM_NUTS_GAMMA) * ad.h_bar);
+        eta = mm_expT(-ST(MM_NUTS_KAPPA) * mm_logT(_m)); /* m^-kappa */
+        ad.epsilon_bar = mm_expT((ST(1) - eta) * mm_logT(ad.epsilon_bar) + eta * mm_logT(ad.epsilon));
+    } else {
+        ad.epsilon = ad.epsilon_bar;
+    }
+}
+
+/* the adaptation record a kernel gives a lane without a chain (it takes no transition; the values are never written back) */
+template <class ST> MM_HD mm_nuts_adapt<ST> mm_nuts_adapt_padding()
+{
+    mm_nuts_adapt<ST> ad;
+    ad.epsilon = ST(0.1);
+    ad.epsilon_bar = ST(1);
+    ad.h_bar = ST(0);
+    ad.mu = ST(0);
+    return ad;
 }
 
 MM_HD bool mm_is_real(float x) { return x == x && x != MM_INFINITY_F && x != -MM_INFINITY_F; }
@@ -410,6 +443,24 @@ struct mm_nuts_tree : Met, Rec {
         }
     }
 
+  private:
+    /* S is a first child, still valid: it waits on the stack for its sibling */
+    MM_HD void push(const mm_nuts_stack<TT, ST, Tgt::dim> &stk)
+    {
+        MM_UNROLL
+        for (int i = 0; i < D; ++i) {
+            stk.v(sp, 0, i) = S_first_x[i];
+            stk.v(sp, 1, i) = S_first_p[i];
+            stk.v(sp, 2, i) = S_prime[i];
+        }
+        stk.a(sp) = S_alpha;
+        stk.c(sp, 0) = S_level;
+        stk.c(sp, 1) = S_n;
+        stk.c(sp, 2) = S_nalpha;
+        sp += 1;
+    }
+
+  public:
     /* one step of handing S up the (implicit) recursion */
     enum { HAND_MORE = 0, HAND_NEXT_LEAF = 1, HAND_DONE = 2 };
     template <bool PRE = false>
@@ -433,10 +484,7 @@ struct mm_nuts_tree : Met, Rec {
             const int e = sp - 1;
             const uint32_t n1 = stk.c(e, 1);
             const double u = draw(); /* always f64 (nuts.rs:910) */
-            uint32_t den = n1 + S_n;
-            if (den < 1)
-                den = 1;
-            const bool take2 = u < ((double)S_n / (double)den);
+            const bool take2 = mm_nuts_take2(u, n1, S_n);
             TT fx[D], fp[D];
             MM_UNROLL
             for (int i = 0; i < D; ++i) {
@@ -460,17 +508,7 @@ struct mm_nuts_tree : Met, Rec {
             sp -= 1;
         } else if (S_s) {
             /* first child, still valid: wait for the sibling */
-            MM_UNROLL
-            for (int i = 0; i < D; ++i) {
-                stk.v(sp, 0, i) = S_first_x[i];
-                stk.v(sp, 1, i) = S_first_p[i];
-                stk.v(sp, 2, i) = S_prime[i];
-            }
-            stk.a(sp) = S_alpha;
-            stk.c(sp, 0) = S_level;
-            stk.c(sp, 1) = S_n;
-            stk.c(sp, 2) = S_nalpha;
-            sp += 1;
+            push(stk);
             return HAND_NEXT_LEAF;
         } else {
             /* first child with s' = 0: the parent returns it as it is (nuts.rs:858 not taken) */
@@ -507,10 +545,7 @@ struct mm_nuts_tree : Met, Rec {
     MM_HD int pair_second(double u)
     {
         const uint32_t n1 = L0_n;
-        uint32_t den = n1 + S_n;
-        if (den < 1)
-            den = 1;
-        const bool take2 = u < ((double)S_n / (double)den);
+        const bool take2 = mm_nuts_take2(u, n1, S_n);
         MM_UNROLL
         for (int i = 0; i < D; ++i)
             if (!take2)
@@ -536,17 +571,7 @@ struct mm_nuts_tree : Met, Rec {
         if (S_level == (uint32_t)j)
             return HAND_DONE;
         if (S_s) {
-            MM_UNROLL
-            for (int i = 0; i < D; ++i) {
-                stk.v(sp, 0, i) = S_first_x[i];
-                stk.v(sp, 1, i) = S_first_p[i];
-                stk.v(sp, 2, i) = S_prime[i];
-            }
-            stk.a(sp) = S_alpha;
-            stk.c(sp, 0) = S_level;
-            stk.c(sp, 1) = S_n;
-            stk.c(sp, 2) = S_nalpha;
-            sp += 1;
+            push(stk);
             return HAND_NEXT_LEAF;
         }
         S_level += 1;
@@ -615,19 +640,9 @@ struct mm_nuts_tree : Met, Rec {
         return d;
     }
 
-    /* dual averaging (nuts.rs:676-690) */
     MM_HD void finish(mm_nuts_adapt<ST> *ad, uint32_t n_discard, ST target_accept_p) const
     {
-        ST eta = ST(1) / (ST)(m + MM_NUTS_T0);
-        ad->h_bar = (ST(1) - eta) * ad->h_bar + eta * (target_accept_p - alpha / (ST)n_alpha);
-        if (m <= n_discard) {
-            const ST _m = (ST)m;
-            ad->epsilon = mm_expT(ad->mu - mm_sqrtT(_m) / ST(MM_NUTS_GAMMA) * ad->h_bar);
-            eta = mm_expT(-ST(MM_NUTS_KAPPA) * mm_logT(_m)); /* m^-kappa */
-            ad->epsilon_bar = mm_expT((ST(1) - eta) * mm_logT(ad->epsilon_bar) + eta * mm_logT(ad->epsilon));
-        } else {
-            ad->epsilon = ad->epsilon_bar;
-        }
+        mm_nuts_dual_average(*ad, m, n_discard, target_accept_p, alpha, n_alpha);
     }
 };
 

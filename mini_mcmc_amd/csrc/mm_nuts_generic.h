@@ -224,10 +224,7 @@ MM_HD mm_nuts_info mm_gen_nuts_step(int kind, const mm_tparams<TT> &P, const S &
                     const int vfx = MM_NV_STACK0 + 3 * e, vfp = vfx + 1, vpr = vfx + 2;
                     const uint32_t n1 = stk_n[e];
                     const double u = aux(); /* always f64 (nuts.rs:910) */
-                    uint32_t den = n1 + S_n;
-                    if (den < 1)
-                        den = 1;
-                    const bool take2 = u < ((double)S_n / (double)den);
+                    const bool take2 = mm_nuts_take2(u, n1, S_n);
                     if (!take2)
                         mm_gen_copy(s, MM_NV_SPR, vpr);
                     S_n += n1;
@@ -277,17 +274,7 @@ MM_HD mm_nuts_info mm_gen_nuts_step(int kind, const mm_tparams<TT> &P, const S &
         info.depth = j;
     }
 
-    /* ---- dual averaging (nuts.rs:676-690; mm_nuts_tree::finish) ---- */
-    ST eta = ST(1) / (ST)(m + MM_NUTS_T0);
-    ad->h_bar = (ST(1) - eta) * ad->h_bar + eta * (target_accept_p - alpha / (ST)n_alpha);
-    if (m <= n_discard) {
-        const ST _m = (ST)m;
-        ad->epsilon = mm_expT(ad->mu - mm_sqrtT(_m) / ST(MM_NUTS_GAMMA) * ad->h_bar);
-        eta = mm_expT(-ST(MM_NUTS_KAPPA) * mm_logT(_m));
-        ad->epsilon_bar = mm_expT((ST(1) - eta) * mm_logT(ad->epsilon_bar) + eta * mm_logT(ad->epsilon));
-    } else {
-        ad->epsilon = ad->epsilon_bar;
-    }
+    mm_nuts_dual_average(*ad, m, n_discard, target_accept_p, alpha, n_alpha);
     return info;
 }
 

@@ -153,10 +153,7 @@ __device__ __forceinline__ void mm_nuts_run_body(const mm_nuts_args<TT, ST> &a, 
     if (active) {
         ad = a.adapt[c];
     } else {
-        ad.epsilon = ST(0.1);
-        ad.epsilon_bar = ST(1);
-        ad.h_bar = ST(0);
-        ad.mu = ST(0);
+        ad = mm_nuts_adapt_padding<ST>();
     }
     unsigned long long n_lf = 0;
     unsigned int m = a.m0;
@@ -261,10 +258,7 @@ __global__ __launch_bounds__(64) void mm_nuts_async_kernel(const mm_nuts_args<TT
     if (active) {
         ad = a.adapt[c];
     } else {
-        ad.epsilon = ST(0.1);
-        ad.epsilon_bar = ST(1);
-        ad.h_bar = ST(0);
-        ad.mu = ST(0);
+        ad = mm_nuts_adapt_padding<ST>();
     }
     const unsigned int total = a.n_pre + a.n_rec;
     TT *const rows = a.out ? a.out + (c * a.n_total + a.out_t0) * D : nullptr; /* this chain's first row */
@@ -415,10 +409,7 @@ __device__ __forceinline__ void mm_nuts_pair_body(const mm_nuts_args<TT, ST> &a,
     if (active) {
         ad = a.adapt[c];
     } else {
-        ad.epsilon = ST(0.1);
-        ad.epsilon_bar = ST(1);
-        ad.h_bar = ST(0);
-        ad.mu = ST(0);
+        ad = mm_nuts_adapt_padding<ST>();
     }
     const unsigned int total = a.n_pre + a.n_rec;
     TT *const rows = a.out ? a.out + (c * a.n_total + a.out_t0) * D : nullptr; /* this chain's first row */

@@ -759,10 +759,7 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
             L.aux_k += 1;
             const unsigned long long cnt = (unsigned long long)__double_as_longlong(cnt_d);
             const unsigned int n1 = (unsigned int)cnt, na1 = (unsigned int)(cnt >> 32);
-            unsigned int den = n1 + S_n;
-            if (den < 1)
-                den = 1;
-            take2 = u < ((double)S_n / (double)den);
+            take2 = mm_nuts_take2(u, n1, S_n);
             S_n += n1;
             S_alpha = alpha + S_alpha;
             S_nalpha += na1;
@@ -982,10 +979,7 @@ __device__ __forceinline__ void mm_lg_doubling(mm_lg_lane<D> &L, const mm_nuts_l
             }
             mm_lg_group_sum2(ca, cb, &ca, &cb);
             const bool crit = neg ? (ca <= 0.0 && cb <= 0.0) : (ca >= 0.0 && cb >= 0.0);
-            unsigned int den = n1 + S_n;
-            if (den < 1)
-                den = 1;
-            const bool take2 = u < ((double)S_n / (double)den);
+            const bool take2 = mm_nuts_take2(u, n1, S_n);
             S_n += n1;
             S_alpha = alpha + S_alpha;
             S_nalpha += na1;
@@ -1370,16 +1364,7 @@ template <int D>
 __device__ __forceinline__ void mm_lg_finish(const mm_lg_lane<D> &L, const mm_nuts_lg_args &a, mm_nuts_adapt<double> &ad,
                                              unsigned int *hist)
 {
-    double eta = 1.0 / (double)(L.m + MM_NUTS_T0);
-    ad.h_bar = (1.0 - eta) * ad.h_bar + eta * (a.target_accept_p - L.alpha / (double)L.n_alpha);
-    if (L.m <= a.n_discard) {
-        const double _m = (double)L.m;
-        ad.epsilon = mm_exp(ad.mu - sqrt(_m) / MM_NUTS_GAMMA * ad.h_bar);
-        eta = mm_exp(-MM_NUTS_KAPPA * mm_log(_m));
-        ad.epsilon_bar = mm_exp((1.0 - eta) * mm_log(ad.epsilon_bar) + eta * mm_log(ad.epsilon));
-    } else {
-        ad.epsilon = ad.epsilon_bar;
-    }
+    mm_nuts_dual_average(ad, L.m, a.n_discard, a.target_accept_p, L.alpha, L.n_alpha);
     /* hist: the wave's histogram in LDS where the kernel has one (flushed once: a global atomic per chain and
      * transition, all on a dozen addresses, serialises in L2), else the global one */
     if (hist && L.q == 0)

@@ -686,6 +686,35 @@ def test_nuts_asynchronous_lanes_equal_synchronous_lanes(M, O, mode):
         NUTS(M.dist.GaussianND.ill_conditioned(16, 10.0, 1), M.core.init_with_seed(8, 16, 1), 0.8, mode=1).set_kernel_variant(4)
 
 
+@pytest.mark.parametrize("mode,max_depth", [(0, 10), (1, 10), (2, 10), (0, 2)])
+def test_nuts_per_lane_kernels_with_padding_lanes(M, O, mode, max_depth):
+    """RosenbrockND(3) on 65 chains -- one full wave and one lane beside 63 padding lanes -- through every per-lane run
+    kernel: variant 0 (the wave in step), 4 (asynchronous lanes), 5 (leaves in pairs) and 6 (run-time dimension), run(6, 5)
+    and run(6, 0) (without and with the initial row).  Each kernel's prologue (chain index, position and adaptation load, the
+    padding lane's record), transition close and write-back must give the bytes of variant 0 and of the host twin: sample,
+    positions, adaptation state, leapfrog counts, depth histogram."""
+    from mini_mcmc_amd.nuts import NUTS
+
+    tgt = M.dist.RosenbrockND(3)
+    init = M.core.init_with_seed(65, 3, 19) * 0.7
+    for nc, nd in ((6, 5), (6, 0)):
+        ref, pos, ad, nlf = O.engine_host_nuts_run(mode, O.ROSENBROCK_ND, 3, [], init, 0.8, nc, nd, seed=31, max_depth=max_depth)
+        res = {}
+        for variant in (0, 4, 5, 6):
+            s = NUTS(tgt, init, 0.8, mode=mode).set_seed(31).set_max_depth(max_depth).set_kernel_variant(variant)
+            assert s.kernel_variant == variant
+            out = s._run(nc, nd, False, "numpy")
+            a = s.adapt_state()
+            res[variant] = (out, s.positions(), np.stack([a[k] for k in ("epsilon", "epsilon_bar", "h_bar", "mu")], axis=1),
+                            s.leapfrog_counts(), s.depth_histogram())
+        name = f"mode={mode} max_depth={max_depth} run({nc}, {nd})"
+        for variant in (0, 4, 5, 6):
+            for i, want in enumerate((ref, pos, ad, nlf, res[0][4])):
+                got = res[variant][i]
+                assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), (name, variant, i)
+        assert res[0][4].sum() == 65 * (nc + nd - 1)
+
+
 def test_hmc_lane_group_mfma_f32_bit_exact_vs_host_twin(M, O):
     """The f32 lane-group kernel (mm_hmc_lg.h, second half: v_mfma_f32_16x16x4_f32, lane (c, q) owning the coordinates
     16 (s >> 2) + 4 q + (s & 3)) against its host twin (blocked reduction order, columns of A x in k-step order), bit for
